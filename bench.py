@@ -23,11 +23,19 @@ Multi-rank runs write the file together (each rank generates its segments),
 and each rank copies only its split's bytes to its GPU; the only collectives
 are metadata all_gathers and the max-over-ranks timing all_reduce.
 
-Prints ONE JSON line (rank 0).  Side legs at N=1 (rank 0): CPU baseline (the
-oracle at 1 thread and on every usable host core), in-session PMC traffic of
-the dominant kernel (rocprofv3 child runs), the drop-in call end to end
-(hbam_open -> hbam_decode_span batches -> pinned host columns), C3 / C5 at
-60 GB, C4 long reads, write-path legs.
+Prints ONE JSON line (rank 0).  A plain run (`--gpus N --steps K --warmup W`)
+builds the file, makes the split resident, warms up, times the K steps and
+prints the headline: value (GB/s of inflated bytes), ms_per_step, records/s.
+--dump-outputs DIR also writes what the timed path computed (dump_outputs).
+
+--full adds everything else, after the timed steps: the untimed measurement
+passes (per-stage times, roofline), the digest parity check, and the side
+legs.  At N=1 (rank 0): CPU baseline (the oracle at 1 thread and on every
+usable host core), in-session PMC traffic of the dominant kernel (rocprofv3
+child runs), the drop-in call end to end (hbam_open -> hbam_decode_span
+batches -> pinned host columns), C3 / C5 at 60 GB, C4 long reads, write-path
+legs.  At N>1: the feed-inclusive C3 decode, rank 0's solo pass, the oracle
+parity of the whole file and the weak N x C2 leg.
 """
 import argparse
 import glob
@@ -441,6 +449,72 @@ def compose_digests(parts):
     return n, kd, vd
 
 
+DUMP_SPOTS = 16            # sampled places of the split
+DUMP_SPOT_RECORDS = 8192   # consecutive records fetched at each
+DUMP_SPOT_STRIDE = 1 << 16  # candidate places: every 65536th record of the split
+DUMP_STATS = ("n_blocks", "compressed_bytes", "inflated_bytes", "records", "first_voff", "last_voff", "windows",
+              "status")
+
+
+def _limbs(x):
+    """An unsigned 64-bit value as four 16-bit limbs, high first (float64 holds each exactly)."""
+    return [(int(x) >> s) & 0xFFFF for s in (48, 32, 16, 0)]
+
+
+def dump_outputs(folder, f, vs, ve, last, D):
+    """--dump-outputs: what the timed path computed, as float64 .npy files (a
+    few tens of MB, far below 64 MB).  hbam_decode_span_device hands its
+    caller one hbam_gpu_stats and leaves the record columns in HBM, so:
+      stats.npy    the counts and bounds of the struct the LAST TIMED step
+                   returned (DUMP_STATS order);
+      digests.npy  key_xor, voff_sum, key_digest, voff_digest (four 16-bit
+                   limbs each, high first) of every record of the split, from
+                   one untimed repeat of the same call with the digest flag;
+      sample_<column>.npy  the 15 SoA columns of DUMP_SPOT_RECORDS consecutive
+                   records at the split's start and at DUMP_SPOTS - 1 places
+                   drawn (seeded) from every DUMP_SPOT_STRIDE-th record,
+                   copied to the host through hbam_decode_span on the same
+                   ctx; 64-bit columns as (n, 2) high / low 32-bit halves;
+      sample_rest_bytes.npy  the byte sum of each sampled record's
+                   rest-of-record bytes.
+    The file is generated from SEED, so the same arguments give the same
+    arrays run after run.  N > 1: each rank writes its split's arrays with a
+    _rank<r> suffix."""
+    import random
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    sfx = "" if D.world == 1 else f"_rank{D.rank}"
+
+    def save(name, arr):
+        np.save(os.path.join(folder, f"{name}{sfx}.npy"), np.ascontiguousarray(arr, np.float64))
+
+    save("stats", [float(last[k]) for k in DUMP_STATS])
+    dg = f.decode_span_device(vs, ve, timing=False, digest=True)
+    save("digests", [_limbs(dg[k]) for k in ("key_xor", "voff_sum", "key_digest", "voff_digest")])
+    _, ent = f.splitting_entries(vs, ve, DUMP_SPOT_STRIDE, 0)
+    spots = [int(v) for v in ent if vs <= int(v) < ve]
+    if len(spots) > DUMP_SPOTS - 1:
+        spots = random.Random(SEED).sample(spots, DUMP_SPOTS - 1)
+    cols, rest = {}, []
+    for v in [vs] + sorted(spots):
+        b = f.decode_span(v, ve, max_records=DUMP_SPOT_RECORDS)
+        for name, arr in b.items():
+            if isinstance(arr, np.ndarray):
+                cols.setdefault(name, []).append(arr)
+        data = np.frombuffer(b["data"], np.uint8)
+        off = b["rest_off"].astype(np.int64)
+        csum = np.concatenate(([0], np.cumsum(data, dtype=np.int64)))
+        rest.append(csum[off + b["rest_len"].astype(np.int64)] - csum[off])
+    for name, parts in cols.items():
+        a = np.concatenate(parts)
+        if a.dtype.itemsize == 8:
+            a = a.view(np.uint64)
+            a = np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF)], axis=1)
+        save("sample_" + name, a)
+    save("sample_rest_bytes", np.concatenate(rest))
+    log(f"[rank {D.rank}] outputs written to {folder}")
+
+
 def bound_of(limits):
     """roofline.bound from the measured limits (fractions of each unit's
     peak): the largest one's unit when it reaches BOUND_MIN, else "latency"
@@ -477,7 +551,7 @@ def roofline_of(stats, world=1):
                            "frac": round(b_alg / (st["ms_total"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)}}
 
 
-def run_c3(D, target_gb, steps, warmup, host_leg=False, solo=False):
+def run_c3(D, target_gb, steps, warmup, host_leg=False, solo=False, full=True, dump=None):
     """C3 / C5 (strong scaling): the ranks split ONE ~60 GB BAM by BGZF byte
     ranges (hbam/shard.py: BAMInputFormat.addProbabilisticSplits on the GPU
     guesser), prefetch their split's bytes to HBM and time `steps` decodes of
@@ -487,7 +561,9 @@ def run_c3(D, target_gb, steps, warmup, host_leg=False, solo=False):
     ordinals (hbam_splitting_entries), gathered on rank 0.  Rank 0 checks
     both against the oracle run over the whole file on every usable core.
     host_leg (N=1): first a decode with the windows copied from the mapped
-    file inside the timed call (PCIe-inclusive)."""
+    file inside the timed call (PCIe-inclusive).  full=False: the timed steps
+    only (no measurement, digest, index or oracle passes, no host_leg / solo).
+    dump: the folder of --dump-outputs."""
     import numpy as np
     import hbam
     from hbam import shard
@@ -532,9 +608,22 @@ def run_c3(D, target_gb, steps, warmup, host_leg=False, solo=False):
         D.barrier()
         t = time.perf_counter()
         for _ in range(steps):
-            step()
+            last = step()
         D.barrier()
         elapsed = D.max_over_ranks(time.perf_counter() - t)
+        if dump and split is not None:
+            dump_outputs(dump, f, vs, ve, last, D)
+        if not full:
+            # a plain run: the headline figures and the last timed step's record counts
+            recs = D.all_gather(0 if last is None else int(last["records"]))
+            f.close()
+            if D.rank != 0:
+                return None
+            u = meta["uncompressed_bytes"]
+            res.update({"value": u * steps / elapsed / 1e9, "ms_per_step": elapsed / steps * 1e3,
+                        "records_per_s": meta["records"] * steps / elapsed, "records": sum(recs),
+                        "split_bytes_rank0": hi - lo, "prefetch_seconds_rank0": round(pf, 3)})
+            return res
         meas = step(timing=True)
         dig = step(digest=True)
         mine = (0, 0, 0) if dig is None else (int(dig["records"]), int(dig["key_digest"]), int(dig["voff_digest"]))
@@ -767,10 +856,13 @@ class Dist:
             self.dist.destroy_process_group()
 
 
-def run_c2(D, args, steps, warmup, extras):
+def run_c2(D, args, steps, warmup, extras, full=True, dump=None):
     """C2 (N=1) / N x C2 weak scaling: every rank decodes one C2 of records
-    from its split of one shared file.  extras (N=1): the CPU baseline, PMC
-    traffic and the side legs, on the same file."""
+    from its split of one shared file.  full: after the timed steps, the
+    untimed measurement passes (stage and kernel times, the roofline), the
+    digest pass and (N > 1) rank 0's solo pass.  extras (N=1, full): the CPU
+    baseline, PMC traffic and the side legs, on the same file.  dump: the
+    folder of --dump-outputs."""
     import hbam
     from hbam import shard
     path = os.path.join(scratch_dir(), f"hbam_bench_{D.tag}.bam")
@@ -796,14 +888,19 @@ def run_c2(D, args, steps, warmup, extras):
         D.barrier()
         t = time.perf_counter()
         for _ in range(steps):
-            step(timing=args.serial)  # production launch order (phase A / phase B overlapped), no events
+            last = step(timing=args.serial)  # production launch order (phase A / phase B overlapped), no events
         D.barrier()
         elapsed = D.max_over_ranks(time.perf_counter() - t)
-        # untimed measurement passes: every launch on one stream between its own
-        # HIP events -> per-stage and per-kernel durations (the roofline)
-        stats = [step(timing=True) for _ in range(3)]
-        tokens = f.inflate_token_count() if split is not None else 0  # phase A's output of that pass
-        check = step(timing=args.serial, digest=True)  # untimed: the digests for the parity check
+        if dump and split is not None:
+            dump_outputs(dump, f, vs, ve, last, D)
+        if full:
+            # untimed measurement passes: every launch on one stream between its own
+            # HIP events -> per-stage and per-kernel durations (the roofline)
+            stats = [step(timing=True) for _ in range(3)]
+            tokens = f.inflate_token_count() if split is not None else 0  # phase A's output of that pass
+            check = step(timing=args.serial, digest=True)  # untimed: the digests for the parity check
+        else:
+            stats, tokens, check = [], 0, last  # a plain run: the last timed step's counts, no digests
         mine = (0, 0, 0, 0) if check is None else (int(check["records"]), int(check["inflated_bytes"]),
                                                    int(check["key_digest"]), int(check["voff_digest"]))
         parts = D.all_gather(mine)
@@ -811,7 +908,7 @@ def run_c2(D, args, steps, warmup, extras):
         u_all = sum(p[1] for p in parts)
         assert n_all == D.world * args.records, (n_all, D.world * args.records)
         solo = None
-        if D.world > 1 and not args.no_solo:
+        if D.world > 1 and full and not args.no_solo:
             # the N = 1 figure: rank 0 decodes its own split (one C2) alone
             if D.rank == 0 and split is not None:
                 step(timing=args.serial)
@@ -841,14 +938,18 @@ def run_c2(D, args, steps, warmup, extras):
                            "records_per_gpu": args.records, "file_bytes": size, "uncompressed_bytes": u_file,
                            "split_bytes_rank0": hi - lo,
                            "parallelism": f"FileVirtualSplit per rank x{D.world} (BAMSplitGuesser)"},
-                "parity": {"records": n_all, "key_digest": f"{kd:#018x}", "voff_digest": f"{vd:#018x}"},
-                "link_fallbacks": int(sum(s_["link_fallbacks"] for s_ in stats)),
-                "link_rewalks": int(sum(s_["link_rewalks"] for s_ in stats)),
-                "stages_ms": {k: round(st[k], 3) for k in ("ms_locate", "ms_inflate", "ms_tables", "ms_huff",
-                                                            "ms_lz77", "ms_chain", "ms_decode", "ms_total")},
-                "roofline": roofline_of(stats, D.world),
-                "cpu_baseline": None,
+                "parity": {"records": n_all},
             }
+            if full:
+                out["parity"].update({"key_digest": f"{kd:#018x}", "voff_digest": f"{vd:#018x}"})
+                out.update({
+                    "link_fallbacks": int(sum(s_["link_fallbacks"] for s_ in stats)),
+                    "link_rewalks": int(sum(s_["link_rewalks"] for s_ in stats)),
+                    "stages_ms": {k: round(st[k], 3) for k in ("ms_locate", "ms_inflate", "ms_tables", "ms_huff",
+                                                                "ms_lz77", "ms_chain", "ms_decode", "ms_total")},
+                    "roofline": roofline_of(stats, D.world),
+                    "cpu_baseline": None,
+                })
         f.close()
         if D.rank == 0 and extras:
             if not args.no_cpu_baseline:
@@ -1046,6 +1147,15 @@ def main():
     ap.add_argument("--workload", choices=("c2", "c3"), default=None,
                     help="c2: C2 per rank (weak); c3: one ~60 GB BAM split over the ranks (strong). "
                          "Default: c2 at one GPU, c3 at N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything else the benchmark measures and checks: the "
+                         "per-stage / roofline passes, the digest parity against the oracle, the CPU baselines, "
+                         "the PMC child runs and the side legs (drop-in, C3 / C5 at 60 GB, C4, write path, pinned "
+                         "host; N > 1: feed-inclusive leg, solo pass, weak N x C2).  The --no-* options below "
+                         "trim a --full run; without --full none of it runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed (the last step's stats, the "
+                         "split's digests, a seeded sample of the record columns) as DIR/<name>.npy")
     ap.add_argument("--records", type=int, default=10_000_000, help="C2 records per rank (10M)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -1077,6 +1187,8 @@ def main():
         return
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if os.environ.get("WORLD_SIZE") is None and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
     check_world(args)
@@ -1092,12 +1204,13 @@ def main():
         D.close()
         return
     workload = args.workload or ("c2" if D.world == 1 else "c3")
+    full = args.full
     line = None
     if workload == "c2":
-        r = run_c2(D, args, args.steps, args.warmup, extras=D.world == 1)
+        r = run_c2(D, args, args.steps, args.warmup, extras=full and D.world == 1, full=full, dump=args.dump_outputs)
         if D.rank == 0:
             line = dict(r, scaling="weak", workload_key="c2")
-        if D.world == 1 and not args.no_extra and args.c3_gb > 0:
+        if full and D.world == 1 and not args.no_extra and args.c3_gb > 0:
             t = time.time()
             try:
                 c3 = run_c3(D, args.c3_gb, steps=3, warmup=1, host_leg=True)
@@ -1106,7 +1219,8 @@ def main():
             log(f"[extra] c3_c5_60GB {time.time() - t:.1f}s")
             if D.rank == 0:
                 line.setdefault("extra", {})["c3_c5_60GB"] = c3
-        if D.world == 1 and not args.no_extra and (args.extras is None or "c2_from_pinned_host" in args.extras):
+        if full and D.world == 1 and not args.no_extra and (args.extras is None or
+                                                            "c2_from_pinned_host" in args.extras):
             # last of all: after hbam_gpu_run_streamed has run in a process, the
             # drop-in loop of a later context ran at ~24 instead of ~40 GB/s U
             # (scripts/dropin_probe2.py --steps)
@@ -1130,7 +1244,8 @@ def main():
             log(f"[extra] c2_from_pinned_host {time.time() - t:.1f}s")
             line.setdefault("extra", {})["c2_from_pinned_host"] = ph
     else:
-        r = run_c3(D, args.c3_gb, args.steps, args.warmup, host_leg=not args.no_feed_leg, solo=not args.no_solo)
+        r = run_c3(D, args.c3_gb, args.steps, args.warmup, host_leg=full and not args.no_feed_leg,
+                   solo=full and not args.no_solo, full=full, dump=args.dump_outputs)
         if D.rank == 0:
             solo = r.get("solo")
             line = {"value": r["value"], "ms_per_step": r["ms_per_step"], "records_per_s": r["records_per_s"],
@@ -1149,12 +1264,14 @@ def main():
                                "records": r["file"]["records"], "layout": r["file"]["layout"],
                                "split_bytes_rank0": r["split_bytes_rank0"],
                                "parallelism": f"FileVirtualSplit per rank x{D.world} (BAMSplitGuesser)"},
-                    "parity": {"records": r["records"], "matches_oracle": r["matches_oracle"],
-                               "c3": r["c3_parity"], "c5_splitting_bai_g4096": r["c5_splitting_bai_g4096"]},
-                    "feed_inclusive": r.get("c3_streamed_from_host"),
-                    "stages_ms": r["stages_ms_rank0"], "windows_rank0": r["windows_rank0"],
-                    "roofline": r["roofline"], "cpu_baseline": r["cpu_baseline"]}
-        if D.world > 1 and not args.no_extra:
+                    "parity": {"records": r["records"]}}
+            if full:
+                line["parity"].update({"matches_oracle": r["matches_oracle"], "c3": r["c3_parity"],
+                                       "c5_splitting_bai_g4096": r["c5_splitting_bai_g4096"]})
+                line.update({"feed_inclusive": r.get("c3_streamed_from_host"),
+                             "stages_ms": r["stages_ms_rank0"], "windows_rank0": r["windows_rank0"],
+                             "roofline": r["roofline"], "cpu_baseline": r["cpu_baseline"]})
+        if full and D.world > 1 and not args.no_extra:
             # the C3 contexts are closed: their cached device blocks go back to
             # HIP first (with --one-device the ranks share one GPU's HBM)
             import gc
@@ -1177,6 +1294,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(line.pop("ms_per_step"), 3),
+            "full": full,
             "higher_is_better": True,
             "scaling": line.pop("scaling"),
             "vs_baseline": None,

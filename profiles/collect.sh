@@ -4,7 +4,8 @@
 #   2. PMC pass FETCH_SIZE, 3. PMC pass WRITE_SIZE (separate passes: TCC slots)
 #   4. PMC pass of SQ counters (VALU / LDS / bank conflicts / occupancy)
 # then summarises everything into $OUT/summary.json (profiles/summarize.py).
-# Only the C2 headline runs under the profiler (--no-extra): the side
+# Only the C2 headline and its measurement passes run under the profiler
+# (--full --no-extra --no-cpu-baseline --no-pmc): the side
 # measurements would add launches of other sizes to the per-kernel averages.
 # --serial: every step in the measurement launch order (one stream), so the
 # per-kernel averages are the kernel durations bench.py's roofline uses.
@@ -15,8 +16,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --no-cpu-baseline --no-extra --no-pmc --serial $*"
-PMCB="python3 $R/bench.py --no-cpu-baseline --no-extra --no-pmc --serial --steps 1 --warmup 0 $*"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --no-extra --no-pmc --serial $*"
+PMCB="python3 $R/bench.py --full --no-cpu-baseline --no-extra --no-pmc --serial --steps 1 --warmup 0 $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- $BENCH \
   > $OUT/trace_bench.json 2> $OUT/trace.err || { echo "trace pass failed"; tail -5 $OUT/trace.err; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- $PMCB \

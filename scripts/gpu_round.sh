@@ -17,11 +17,11 @@ for s in $STEPS; do
         > $OUT/pytest_gpu.log 2>&1 || { echo "gpu tests failed"; tail -30 $OUT/pytest_gpu.log; exit 1; }
       tail -2 $OUT/pytest_gpu.log ;;
     bench)
-      timeout -k 10 420 python -u bench.py --steps 10 --warmup 3 --no-extra > $OUT/bench.json 2> $OUT/bench.err \
+      timeout -k 10 420 python -u bench.py --full --steps 10 --warmup 3 --no-extra > $OUT/bench.json 2> $OUT/bench.err \
         || { echo "bench failed"; tail -30 $OUT/bench.err; exit 2; }
       cat $OUT/bench.json ;;
     benchfull)
-      timeout -k 10 900 python -u bench.py --steps 20 --warmup 5 > $OUT/bench_full.json 2> $OUT/bench_full.err \
+      timeout -k 10 900 python -u bench.py --full --steps 20 --warmup 5 > $OUT/bench_full.json 2> $OUT/bench_full.err \
         || { echo "bench failed"; tail -30 $OUT/bench_full.err; exit 2; }
       cat $OUT/bench_full.json ;;
     reader)
@@ -29,7 +29,7 @@ for s in $STEPS; do
         > $OUT/pytest_reader.log 2>&1 || { echo "reader tests failed"; tail -40 $OUT/pytest_reader.log; exit 1; }
       tail -2 $OUT/pytest_reader.log ;;
     hostlegs)
-      timeout -k 10 600 python -u bench.py --steps 5 --warmup 2 --no-pmc --extras dropin_end_to_end --c3-gb 20 \
+      timeout -k 10 600 python -u bench.py --full --steps 5 --warmup 2 --no-pmc --extras dropin_end_to_end --c3-gb 20 \
         > $OUT/bench_host.json 2> $OUT/bench_host.err || { echo "bench failed"; tail -30 $OUT/bench_host.err; exit 2; }
       python3 -c "import json,sys; d=json.load(open('$OUT/bench_host.json')); e=d['extra']; print(json.dumps(e['dropin_end_to_end'])); c=e['c3_c5_60GB']; print(json.dumps({k: c.get(k) for k in ('c3_streamed_from_host','value','matches_oracle')}))" ;;
     large)
@@ -154,7 +154,7 @@ for s in $STEPS; do
         || { echo "collect failed"; tail -30 $OUT/collect.log; exit 8; }
       python3 -c "import json; d=json.load(open('$R/gpurun_out/prof_$TAG/summary.json'))['kernels']; [print('%-45s calls %4d main_avg_us %9.1f' % (k[:45], v['calls'], v.get('main_avg_ns', 0) / 1e3)) for k, v in sorted(d.items(), key=lambda x: -x[1].get('total_ns', 0))[:22]]" ;;
     rehearsal)
-      timeout -k 10 600 python -u bench.py --gpus 2 --dist-backend gloo --one-device --c3-gb 7 --steps 3 --warmup 1 \
+      timeout -k 10 600 python -u bench.py --full --gpus 2 --dist-backend gloo --one-device --c3-gb 7 --steps 3 --warmup 1 \
         > $OUT/rehearsal.json 2> $OUT/rehearsal.err || { echo "rehearsal failed"; tail -30 $OUT/rehearsal.err; exit 3; }
       cat $OUT/rehearsal.json ;;
     smoke)
@@ -163,7 +163,7 @@ for s in $STEPS; do
       tail -2 $OUT/smoke.log ;;
     rehearsal8)
       # the driver's 8-GPU sequence with 8 gloo ranks sharing this box's one GPU
-      timeout -k 10 900 python -u bench.py --gpus 8 --dist-backend gloo --one-device --c3-gb 4 --steps 3 --warmup 1 \
+      timeout -k 10 900 python -u bench.py --full --gpus 8 --dist-backend gloo --one-device --c3-gb 4 --steps 3 --warmup 1 \
         > $OUT/rehearsal8.json 2> $OUT/rehearsal8.err || { echo "rehearsal8 failed"; tail -30 $OUT/rehearsal8.err; exit 3; }
       cat $OUT/rehearsal8.json ;;
   esac

@@ -1,8 +1,9 @@
-"""Regenerate tests/golden/ (run in the build container; /root/reference is
-not available on the GPU box).
+"""Regenerate tests/golden/ from a checkout of the reference (Hadoop-BAM):
+python tests/golden/make_golden.py <checkout>/src/test/resources.  The tests
+themselves read only the files stored here.
 
 Inputs are data fixtures the reference's own tests hold
-(/root/reference/src/test/resources: test.bam, HiSeq.10000.vcf.bgzf.gz,
+(src/test/resources: test.bam, HiSeq.10000.vcf.bgzf.gz,
 test.vcf.bgzf.gz, test.bgzf.bcf; MIT, LICENSE.txt).  Expected outputs come from
 the C oracle (oracle/hbam_oracle.c), cross-checked against the independent
 Python restatement (oracle/py_oracle.py) and against the pins the reference
@@ -26,10 +27,10 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import orc  # noqa: E402
 import py_oracle  # noqa: E402
 
-RES = "/root/reference/src/test/resources"
-
-
 def main():
+    if len(sys.argv) != 2:
+        sys.exit("usage: make_golden.py <Hadoop-BAM checkout>/src/test/resources")
+    RES = sys.argv[1]
     for f in ("test.bam", "HiSeq.10000.vcf.bgzf.gz", "test.vcf.bgzf.gz", "test.bgzf.bcf"):
         shutil.copyfile(os.path.join(RES, f), os.path.join(HERE, f))
     bam = open(os.path.join(HERE, "test.bam"), "rb").read()

@@ -47,6 +47,16 @@ def test_failing_rank_fails_the_run():
     assert p.returncode != 0
 
 
+def test_full_and_dump_options_exist_and_steps_must_be_positive():
+    """A plain run is the headline only; --full and --dump-outputs are options
+    of their own, and --steps sets the number of timed steps (0 is refused)."""
+    p = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=60, env=_env())
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs DIR" in p.stdout
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--dry-run"], capture_output=True,
+                       text=True, timeout=60, env=_env())
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
 def test_inflate_rounds_match_the_library():
     """bench.py divides phase A's time over INFLATE_ROUNDS launches per chunk:
     it must be the library's kInflateRounds (HBAM_INFLATE_ROUNDS default)."""

@@ -6,6 +6,7 @@ hbam_* call of the glue is declared in include/hbam.h, and every HbamNative
 method the delegating classes (GpuBAMRecordReader, GpuBAMInputFormat,
 GpuSplittingBAMIndexer, GpuSAMRecordWritable, GpuBAMRecordWriter) call exists
 with that arity."""
+import json
 import os
 import re
 
@@ -92,7 +93,11 @@ def test_reader_mirrors_the_reference_reader_surface():
     assert "SAMRecordFactory factory = DefaultSAMRecordFactory.getInstance()" in src
 
 
-REF_INDEXER = "/root/reference/src/main/java/org/seqdoop/hadoop_bam/SplittingBAMIndexer.java"
+def _reference_api(cls):
+    """The reference class's public (name, parameter types), as stored in
+    tests/golden/reference_api.json under the Gpu* class that mirrors it."""
+    api = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_api.json")))
+    return {(n, tuple(t)) for n, t in api[cls]}
 
 
 def _public_signatures(src):
@@ -109,15 +114,8 @@ def test_gpu_indexer_has_the_reference_indexer_api():
     SplittingBAMIndexer (SplittingBAMIndexer.java:72-290) with the same
     parameter types (the deprecated granularity-only constructor aside)."""
     gpu = _strip_comments(open(os.path.join(JAVA, "GpuSplittingBAMIndexer.java")).read())
-    if os.path.exists(REF_INDEXER):
-        ref = _public_signatures(_strip_comments(open(REF_INDEXER).read()))
-        ref = {("GpuSplittingBAMIndexer" if n == "SplittingBAMIndexer" else n, t) for n, t in ref
-               if (n, t) != ("SplittingBAMIndexer", ("int",)) and n != "PtrSkipPair"}  # (a private helper class)
-    else:  # the reference's list, as read from the file above when it was present
-        ref = {("main", ("String[]",)), ("run", ("Configuration",)),
-               ("index", ("InputStream", "OutputStream", "long", "int")),
-               ("GpuSplittingBAMIndexer", ("OutputStream",)), ("GpuSplittingBAMIndexer", ("OutputStream", "int")),
-               ("processAlignment", ("SAMRecord",)), ("writeVirtualOffset", ("long",)), ("finish", ("long",))}
+    ref = _reference_api("GpuSplittingBAMIndexer")
+    assert len(ref) == 8
     have = _public_signatures(gpu)
     assert ref <= have, ref - have
 
@@ -132,9 +130,6 @@ def test_write_time_indexer_keeps_o1_state():
     assert "long[] voffs" not in src and "Arrays.copyOf" not in src
 
 
-REF = "/root/reference/src/main/java/org/seqdoop/hadoop_bam"
-
-
 def test_gpu_guesser_has_the_reference_guesser_api():
     """GpuBAMSplitGuesser offers BAMSplitGuesser's public entry points
     (BAMSplitGuesser.java:80-108): both constructors and the guess, on the
@@ -143,14 +138,8 @@ def test_gpu_guesser_has_the_reference_guesser_api():
     reference's command-line main (:340-401) is out of scope and absent."""
     src = _strip_comments(open(os.path.join(JAVA, "GpuBAMSplitGuesser.java")).read())
     assert "class GpuBAMSplitGuesser extends BaseSplitGuesser" in src
-    ref_file = os.path.join(REF, "BAMSplitGuesser.java")
-    if os.path.exists(ref_file):
-        ref = _public_signatures(_strip_comments(open(ref_file).read()))
-        ref = {("GpuBAMSplitGuesser" if n == "BAMSplitGuesser" else n, t) for n, t in ref if n != "main"}
-    else:  # the reference's list, as read from the file above when it was present
-        ref = {("GpuBAMSplitGuesser", ("SeekableStream", "Configuration")),
-               ("GpuBAMSplitGuesser", ("SeekableStream", "InputStream", "Configuration")),
-               ("guessNextBAMRecordStart", ("long", "long"))}
+    ref = _reference_api("GpuBAMSplitGuesser")
+    assert len(ref) == 3
     have = _public_signatures(src)
     assert ref <= have, ref - have
     assert not any(n == "main" for n, _ in have)
@@ -170,14 +159,8 @@ def test_writable_and_writer_mirror_the_reference_surface():
     assert {("write", ("DataOutput",)), ("readFields", ("DataInput",)), ("set", ("SAMRecord",))} <= have
     r = _strip_comments(open(os.path.join(JAVA, "GpuBAMRecordWriter.java")).read())
     assert "extends RecordWriter<K, SAMRecordWritable>" in r
-    if os.path.exists(os.path.join(REF, "BAMRecordWriter.java")):
-        ref = _public_signatures(_strip_comments(open(os.path.join(REF, "BAMRecordWriter.java")).read()))
-        ref = {("GpuBAMRecordWriter" if n == "BAMRecordWriter" else n, t) for n, t in ref}
-    else:  # the reference's list, as read from the file above when it was present
-        ref = {("GpuBAMRecordWriter", ("Path", "Path", "boolean", "TaskAttemptContext")),
-               ("GpuBAMRecordWriter", ("Path", "SAMFileHeader", "boolean", "TaskAttemptContext")),
-               ("GpuBAMRecordWriter", ("OutputStream", "SAMFileHeader", "boolean")),
-               ("close", ("TaskAttemptContext",))}
+    ref = _reference_api("GpuBAMRecordWriter")
+    assert len(ref) == 4
     assert ref <= _public_signatures(r), ref - _public_signatures(r)
     assert "protected void writeAlignment(final SAMRecord rec)" in r
     k = _strip_comments(open(os.path.join(JAVA, "GpuKeyIgnoringBAMRecordWriter.java")).read())
