@@ -26,6 +26,7 @@ using hadoop_bam::FileSplit;
 using hadoop_bam::FileVirtualSplit;
 using hadoop_bam::HostBatch;
 using hadoop_bam::OpenOptions;
+using hadoop_bam::QueryCursor;
 using hadoop_bam::SpanCursor;
 using hadoop_bam::SplittingBAMIndexer;
 using hadoop_bam::Step;
@@ -39,7 +40,16 @@ struct hbam_ctx {
   hadoop_bam::BatchView batch;  // the last batch handed out (cursor slots or wbatch)
   hbam::SpanDev wspan;  // device result of the last hbam_decode_writables
   bool last_is_writables = false;
+  std::unique_ptr<QueryCursor> query;  // the open bounded traversal (hbam_query_*), if any
+  bool last_is_query = false;          // the last batch came from hbam_query_next
 };
+
+// Forget the split and the query being read: the call about to run moves the
+// ctx's window.
+static void reset_cursors(hbam_ctx* ctx) {
+  ctx->cursor.reset();
+  ctx->query.reset();
+}
 
 struct hbam_gpu {
   std::unique_ptr<BamFile> f;
@@ -364,7 +374,7 @@ int hbam_ref(hbam_ctx* ctx, int32_t i, const char** name, int32_t* length) {
 
 int hbam_file_stats(hbam_ctx* ctx, uint64_t* n_blocks, uint64_t* uncompressed_size) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();  // all_blocks() moves the window
+  reset_cursors(ctx);  // all_blocks() moves the window
   const std::vector<hbam::BlockInfo>* B = nullptr;
   int rc = ctx->f->all_blocks(&B);
   if (rc != HBAM_OK) {
@@ -388,7 +398,7 @@ int hbam_prefetch(hbam_ctx* ctx, uint64_t lo, uint64_t hi) {
     ctx->err = "prefetch range end before its start";
     return HBAM_E_ARG;
   }
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   int rc = ctx->f->prefetch(lo, hi);
   if (rc != HBAM_OK) ctx->err = ctx->f->error();
   return rc;
@@ -398,6 +408,8 @@ int hbam_decode_span(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, uint64_t max
   memset(out, 0, sizeof *out);
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   ctx->last_is_writables = false;
+  ctx->last_is_query = false;
+  ctx->query.reset();  // a split read ends an open query
   uint64_t next = vend;
   int rc = ctx->cursor.next_batch(*ctx->f, vstart, vend, max_records, &ctx->batch, &next, &ctx->err);
   fill_batch(ctx->batch, out);
@@ -407,10 +419,47 @@ int hbam_decode_span(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, uint64_t max
   return rc;
 }
 
+int hbam_query_intervals(hbam_ctx* ctx, const hbam_interval* iv, uint64_t n_iv, const uint64_t* file_pointers,
+                         uint64_t n_ptrs) {
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  static_assert(sizeof(hbam_interval) == sizeof(hadoop_bam::QueryInterval), "hbam_interval is three int32");
+  reset_cursors(ctx);
+  std::unique_ptr<QueryCursor> q(new QueryCursor());
+  const int rc = q->open_intervals(*ctx->f, reinterpret_cast<const hadoop_bam::QueryInterval*>(iv), n_iv,
+                                   file_pointers, n_ptrs, &ctx->err);
+  if (rc == HBAM_OK) ctx->query = std::move(q);
+  return rc;
+}
+
+int hbam_query_unmapped(hbam_ctx* ctx, uint64_t start_voff) {
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  reset_cursors(ctx);
+  std::unique_ptr<QueryCursor> q(new QueryCursor());
+  const int rc = q->open_unmapped(*ctx->f, start_voff, &ctx->err);
+  if (rc == HBAM_OK) ctx->query = std::move(q);
+  return rc;
+}
+
+int hbam_query_next(hbam_ctx* ctx, uint64_t max_records, hbam_batch* out) {
+  memset(out, 0, sizeof *out);
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  if (!ctx->query) {
+    ctx->err = "hbam_query_next needs an open query (hbam_query_intervals / hbam_query_unmapped)";
+    return HBAM_E_STATE;
+  }
+  ctx->last_is_writables = false;
+  ctx->last_is_query = true;
+  const int rc = ctx->query->next_batch(*ctx->f, max_records, &ctx->batch, &ctx->err);
+  fill_batch(ctx->batch, out);
+  out->status = rc;
+  if (rc == HBAM_E_DEVICE || rc == HBAM_E_STATE || rc == HBAM_E_NOMEM) out->n = 0;
+  return rc;
+}
+
 int hbam_reader_position(hbam_ctx* ctx, uint64_t i, uint64_t* pos) {
   *pos = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  if (ctx->last_is_writables || !ctx->cursor.valid()) {
+  if (ctx->last_is_writables || ctx->last_is_query || !ctx->cursor.valid()) {
     ctx->err = "hbam_reader_position needs the last call on the ctx to be hbam_decode_span";
     return HBAM_E_STATE;
   }
@@ -441,7 +490,7 @@ int hbam_inflate_token_count(hbam_ctx* ctx, uint64_t* tokens) {
 
 int hbam_decode_span_device(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_t flags, hbam_gpu_stats* st) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   return decode_device(*ctx->f, vstart, vend, flags, st, nullptr, &ctx->err);
 }
 
@@ -468,7 +517,7 @@ int hbam_encode_writables(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* o
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   hbam::Pipeline& p = ctx->f->pipe();
   hbam::SpanDev span;
-  if (ctx->last_is_writables || (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
+  if (ctx->last_is_writables || ctx->last_is_query || (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
     ctx->err = "hbam_encode_writables needs a one-window batch from hbam_decode_span";
     return HBAM_E_STATE;
   }
@@ -513,8 +562,9 @@ int hbam_decode_writables(hbam_ctx* ctx, const void* buf, uint64_t len, const ui
   memset(out, 0, sizeof *out);
   if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
   hbam::Pipeline& p = ctx->f ? ctx->f->pipe() : *ctx->codec;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   ctx->last_is_writables = true;
+  ctx->last_is_query = false;
   hbam::SpanDev& span = ctx->wspan;
   span = hbam::SpanDev();
   int rc = p.decode_writables(static_cast<const uint8_t*>(buf), len, offs, n, &span);
@@ -544,7 +594,7 @@ int hbam_build_splitting_index(hbam_ctx* ctx, int32_t granularity, uint8_t** buf
   *buf = nullptr;
   *len = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   std::vector<uint8_t> out;
   int rc = SplittingBAMIndexer::index(*ctx->f, granularity, &out);
   if (rc != HBAM_OK) {
@@ -563,7 +613,7 @@ int hbam_splitting_entries(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_
   *entries = nullptr;
   *n_entries = *n_records = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   std::vector<uint64_t> ent;
   int rc = SplittingBAMIndexer::entries(*ctx->f, vstart, vend, granularity, ordinal0, &ent, n_records);
   if (rc != HBAM_OK) {
@@ -634,7 +684,7 @@ int hbam_guess_record_starts(hbam_ctx* ctx, const uint64_t* begs, const uint64_t
 int hbam_guess_record_starts_hdr(hbam_ctx* ctx, int32_t header_n_ref, const uint64_t* begs, const uint64_t* ends,
                                  uint64_t n, uint64_t* out) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   std::vector<uint64_t> b(begs, begs + n), e(ends, ends + n), r;
   hadoop_bam::BAMSplitGuesser g(*ctx->f, header_n_ref);
   int rc = g.guessNextBAMRecordStarts(b, e, &r);
@@ -649,7 +699,7 @@ int hbam_guess_record_starts_hdr(hbam_ctx* ctx, int32_t header_n_ref, const uint
 int hbam_guess_bgzf_block_starts(hbam_ctx* ctx, const uint64_t* begs, const uint64_t* ends, uint64_t n,
                                  uint64_t* out) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   std::vector<uint64_t> b(begs, begs + n), e(ends, ends + n), r;
   int rc = hadoop_bam::guess_bgzf_batch(*ctx->f, b, e, &r, &ctx->err);
   if (rc != HBAM_OK) return rc;
@@ -667,7 +717,7 @@ int hbam_get_splits_bai(hbam_ctx* ctx, const uint64_t* starts, const uint64_t* l
                         uint64_t* vends, uint64_t* nout) {
   *nout = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   std::vector<FileSplit> sp(n);
   for (uint64_t i = 0; i < n; ++i) {
     sp[i].path = "bam";
@@ -691,7 +741,7 @@ int hbam_get_splits_bai(hbam_ctx* ctx, const uint64_t* starts, const uint64_t* l
 int hbam_blocks(hbam_ctx* ctx, uint64_t* coff, uint32_t* csize, uint32_t* isize, uint64_t* ustart, uint64_t cap,
                 uint64_t* n) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   const std::vector<hbam::BlockInfo>* B = nullptr;
   int rc = ctx->f->all_blocks(&B);
   if (rc != HBAM_OK) {
@@ -710,7 +760,7 @@ int hbam_blocks(hbam_ctx* ctx, uint64_t* coff, uint32_t* csize, uint32_t* isize,
 
 int hbam_read_inflated(hbam_ctx* ctx, uint64_t pos, uint64_t len, uint8_t* dst) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->cursor.reset();
+  reset_cursors(ctx);
   std::vector<uint8_t> v;
   int rc = ctx->f->read_inflated(pos, len, &v);
   if (rc != HBAM_OK) {

@@ -457,6 +457,61 @@ class SpanCursor {
   bool all_one_window_ = false;
 };
 
+// [htsjdk] QueryInterval: 1-based inclusive; end <= 0 = to the end of the reference.
+struct QueryInterval {
+  int32_t ref_id, start, end;
+};
+
+// A bounded traversal being read (BAMRecordReader.initialize's interval and
+// unmapped-only branches, BAMRecordReader.java:170-178; hbam_query_*).  The
+// chunks are decoded one after the other, window by window
+// (BamFile::decode_step, as hbam_decode_span reads a split); each window's
+// records are filtered and compacted on the GPU (hbam_query.h), the kept ones
+// copied to page-locked host memory and handed out in slices.  The filter's
+// interval index (or, unmapped-only, "an unplaced record was seen") is carried
+// from one window and chunk to the next; after the record that ends the
+// iteration no further window is decoded.
+class QueryCursor {
+ public:
+  QueryCursor() = default;
+  QueryCursor(const QueryCursor&) = delete;
+  QueryCursor& operator=(const QueryCursor&) = delete;
+  // createIndexIterator(intervals, false, filePointers): intervals optimized
+  // ([htsjdk] assertIntervalsOptimized), ptrs = n_ptrs / 2 chunks [s, e) in
+  // file order; otherwise kErrArg
+  int open_intervals(BamFile& f, const QueryInterval* iv, uint64_t n_iv, const uint64_t* ptrs, uint64_t n_ptrs,
+                     std::string* err);
+  // queryUnmapped() reading from start_voff
+  int open_unmapped(BamFile& f, uint64_t start_voff, std::string* err);
+  // Up to max_records kept records (0 = all that remain); out->n == 0: the
+  // end.  A failing record's status comes with the last records before it.
+  // A bounded batch holds records of one window and, as SpanCursor's, at
+  // most 2 GiB - 1 KiB of rest bytes (one record at least).
+  int next_batch(BamFile& f, uint64_t max_records, BatchView* out, std::string* err);
+
+ private:
+  // decode windows until one keeps a record (all: until the end), appending to h
+  int advance(BamFile& f, HostBatch* h, bool all, std::string* err);
+  int filter(BamFile& f, const SpanDev& s, HostBatch* h, bool* stop, std::string* err);
+  int begin(BamFile& f, std::string* err);
+
+  bool unmapped_ = false;
+  std::vector<std::pair<uint64_t, uint64_t>> chunks_;
+  size_t chunk_ = 0;
+  bool in_chunk_ = false, cont_ = false, done_ = false;
+  Carry c_;
+  uint32_t n_iv_ = 0, carry_ = 0;  // the filter's interval index after the last record read
+  bool found_ = false;             // unmapped-only: a record with refID -1 was read
+  int status_ = 0;                 // the failing record's status, once every record before it is handed out
+  std::string status_err_;
+  HostBatch win_, all_;            // the kept records of the last window / of a max_records = 0 call
+  uint64_t k_ = 0;                 // next record of win_
+  hbam::DevBuf<int32_t> iv_, aend_;
+  hbam::DevBuf<uint32_t> p_, idx_, flag_, slot_;
+  hbam::DevBuf<uint64_t> klen_, roff_, src_off_, state_;
+  hbam::DevBuf<uint8_t> tmp_, cols_, rests_;
+};
+
 // BAMRecordReader (BAMRecordReader.java:63-233) over one FileVirtualSplit.
 class BAMRecordReader {
  public:

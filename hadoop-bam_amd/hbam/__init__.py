@@ -89,6 +89,9 @@ _sig("hbam_ref", C.c_int, [P, i32, C.POINTER(C.c_char_p), C.POINTER(i32)])
 _sig("hbam_decode_span", C.c_int, [P, u64, u64, u64, C.POINTER(Batch)])
 _sig("hbam_decode_span_device", C.c_int, [P, u64, u64, i32, C.POINTER(GpuStats)])
 _sig("hbam_reader_position", C.c_int, [P, u64, C.POINTER(u64)])
+_sig("hbam_query_intervals", C.c_int, [P, P, u64, P, u64])
+_sig("hbam_query_unmapped", C.c_int, [P, u64])
+_sig("hbam_query_next", C.c_int, [P, u64, C.POINTER(Batch)])
 _sig("hbam_pipeline_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_token_count", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_file_stats", C.c_int, [P, C.POINTER(u64), C.POINTER(u64)])
@@ -486,6 +489,55 @@ class BamFile:
             v = b.next_voff
         self._last_n = b.n
         return n, k, nbytes
+
+    def query_intervals(self, intervals, file_pointers):
+        """Open an interval query (hbam_query_intervals): intervals =
+        [(ref_id, start, end)], optimized; file_pointers = the flat chunk
+        list [s0, e0, s1, e1, ...] of virtual offsets."""
+        iv = np.ascontiguousarray(np.asarray(intervals, np.int32).reshape(-1, 3))
+        fp = np.ascontiguousarray(file_pointers, np.uint64)
+        rc = _L.hbam_query_intervals(self._h, iv.ctypes.data if len(iv) else None, len(iv),
+                                     fp.ctypes.data if len(fp) else None, len(fp))
+        if rc != OK:
+            raise self._err(rc)
+
+    def query_unmapped(self, start_voff):
+        """Open the unmapped-only query (hbam_query_unmapped) reading from start_voff."""
+        rc = _L.hbam_query_unmapped(self._h, start_voff)
+        if rc != OK:
+            raise self._err(rc)
+
+    def query_next(self, max_records=0, raise_on_error=True):
+        """The next records of the open query (at most max_records; 0 = all
+        that remain) as decode_span's dict; no record: the end."""
+        b = Batch()
+        rc = _L.hbam_query_next(self._h, max_records, C.byref(b))
+        if rc != OK and (raise_on_error or rc not in (E_FORMAT, E_TRUNC, E_IO)):
+            raise self._err(rc)
+        self._last_n = b.n
+        return _batch_dict(b, rc)
+
+    def scan_query(self, max_records):
+        """The open query through hbam_query_next in bounded batches, leaving
+        each batch in the library's pinned host columns (no Python copies), as
+        scan_batches does for a split: (records, batches, rest bytes)."""
+        b = Batch()
+        n, k, nbytes = 0, 0, 0
+        while True:
+            rc = _L.hbam_query_next(self._h, max_records, C.byref(b))
+            if rc != OK:
+                raise self._err(rc)
+            if b.n == 0:
+                break
+            n += b.n
+            k += 1
+            nbytes += b.data_len
+        self._last_n = 0
+        return n, k, nbytes
+
+    def query_all(self, raise_on_error=True):
+        """Every remaining record of the open query in one batch."""
+        return self.query_next(0, raise_on_error)
 
     def encode_writables(self):
         """SAMRecordWritable.write of every record of the last decode_span

@@ -167,6 +167,53 @@ int hbam_decode_span(hbam_ctx *ctx, uint64_t vstart, uint64_t vend, uint64_t max
  * handed out (the iterator has read record 0 only). */
 int hbam_reader_position(hbam_ctx *ctx, uint64_t i, uint64_t *pos);
 
+/* ---- bounded traversal (hadoopbam.bam.intervals / hadoopbam.bam.bounded-traversal) ---- */
+/* [htsjdk] QueryInterval: 1-based inclusive; end <= 0 = to the end of the reference. */
+typedef struct hbam_interval { int32_t ref_id, start, end; } hbam_interval;
+/* BAMRecordReader.initialize's interval branch (BAMRecordReader.java:171-175):
+ * bamFileReader.createIndexIterator(queryIntervals, false, filePointers).
+ * iv = the intervals BAMInputFormat.prepareQueryIntervals returns, optimized
+ * (sorted by ref_id, and within one ref_id each start past the previous
+ * interval's end; an end may not lie more than one base before its start):
+ * [htsjdk] assertIntervalsOptimized -> HBAM_E_ARG otherwise.  file_pointers =
+ * FileVirtualSplit.getIntervalFilePointers(): n_ptrs / 2 chunks of virtual
+ * offsets [file_pointers[2k], file_pointers[2k+1]), in ascending order (an odd
+ * n_ptrs or a chunk out of order -> HBAM_E_ARG).  The chunks are read in turn,
+ * each yielding the records hbam_decode_span(start, end) would, and
+ * [htsjdk] BAMQueryFilteringIterator's filter runs over them on the GPU: one
+ * interval index for the whole query, a record kept when the first interval
+ * that does not lie before it overlaps it, and the iteration over -- nothing
+ * further read -- at the first record that lies past every interval.  Records
+ * read are validated under the ctx's stringency whether kept or not.
+ * Opens the query: hbam_query_next returns its records.  The query ends,
+ * and hbam_query_next returns HBAM_E_STATE until another is opened, with any
+ * other call on the ctx that reads the file, since each of them moves the
+ * ctx's window: hbam_decode_span*, hbam_decode_writables, hbam_prefetch,
+ * hbam_file_stats, hbam_blocks, hbam_read_inflated,
+ * hbam_build_splitting_index, hbam_splitting_entries, hbam_get_splits*,
+ * hbam_guess_*.  hbam_header, hbam_ref, hbam_bytes_read,
+ * hbam_pipeline_counters and hbam_last_error leave it open. */
+int hbam_query_intervals(hbam_ctx *ctx, const hbam_interval *iv, uint64_t n_iv, const uint64_t *file_pointers,
+                         uint64_t n_ptrs);
+/* The unmapped-only branch (BAMRecordReader.java:176-178):
+ * bamFileReader.queryUnmapped().  Reads from start_voff
+ * (getIndex().getStartOfLastLinearBin(), or the first record's offset when
+ * that is -1) to the end of the file, skips (and validates) records up to the
+ * first one with refID == -1, and yields every record from it on. */
+int hbam_query_unmapped(hbam_ctx *ctx, uint64_t start_voff);
+/* The next records of the open query, at most max_records (0 = all that
+ * remain), as hbam_decode_span hands them out (out->data holds the rests back
+ * to back); out->n == 0: the end.  out->next_voff is 0.  A batch with
+ * max_records > 0 holds records of one window, so it may be shorter than
+ * asked, and its rests stay below 2 GiB (one record at least), the size a JNI
+ * caller can wrap as a direct ByteBuffer; max_records = 0 has no such bound
+ * (as in hbam_decode_span), so a JNI caller passes a batch size.  Records before a
+ * failing record are returned with out->status set and the call returns that
+ * status; a failing record past the one that ended the iteration is never
+ * read.  No query open -> HBAM_E_STATE.  After a query batch
+ * hbam_encode_writables and hbam_reader_position return HBAM_E_STATE. */
+int hbam_query_next(hbam_ctx *ctx, uint64_t max_records, hbam_batch *out);
+
 /* SplittingBAMIndexer.index(in, out, inputSize, granularity)
  * (SplittingBAMIndexer.java:248-290): the .splitting-bai bytes, big-endian u64
  * entries, byte-identical to the reference; the file is streamed through HBM

@@ -246,6 +246,39 @@ JNIEXPORT jobjectArray FN(decodeSpan)(JNIEnv *env, jclass c, jlong h, jlong vs, 
   return wrap_batch(env, &b);
 }
 
+/* intervals: {ref_id, start, end} triples (QueryInterval.referenceIndex / start / end) */
+JNIEXPORT void FN(queryIntervals)(JNIEnv *env, jclass c, jlong h, jintArray intervals, jlongArray file_pointers) {
+  jsize np;
+  uint64_t *fp = from_longs(env, file_pointers, &np);
+  if (!fp) return;
+  const jsize ni = intervals ? (*env)->GetArrayLength(env, intervals) : 0;
+  jint *iv = ni ? (*env)->GetIntArrayElements(env, intervals, NULL) : NULL;
+  int rc = ni % 3 || (ni && !iv) ? HBAM_E_ARG
+                                 : hbam_query_intervals(CTX(h), (const hbam_interval *)iv, (uint64_t)(ni / 3), fp,
+                                                        (uint64_t)np);
+  if (iv) (*env)->ReleaseIntArrayElements(env, intervals, iv, JNI_ABORT);
+  free(fp);
+  if (rc != HBAM_OK) throw_for(env, rc, ni % 3 ? "intervals are (ref, start, end) triples" : hbam_last_error(CTX(h)));
+}
+
+JNIEXPORT void FN(queryUnmapped)(JNIEnv *env, jclass c, jlong h, jlong start_voff) {
+  int rc = hbam_query_unmapped(CTX(h), (uint64_t)start_voff);
+  if (rc != HBAM_OK) throw_for(env, rc, hbam_last_error(CTX(h)));
+}
+
+JNIEXPORT jobjectArray FN(queryNext)(JNIEnv *env, jclass c, jlong h, jlong max_records) {
+  hbam_batch b;
+  memset(&b, 0, sizeof b);
+  int rc = hbam_query_next(CTX(h), (uint64_t)max_records, &b);
+  /* records before a failing one are delivered; the status stays with the
+   * query, so the next call (the reader's next nextKeyValue) throws */
+  if (rc != HBAM_OK && b.n == 0) {
+    throw_for(env, rc, hbam_last_error(CTX(h)));
+    return NULL;
+  }
+  return wrap_batch(env, &b);
+}
+
 JNIEXPORT jlong FN(readerPosition)(JNIEnv *env, jclass c, jlong h, jlong i) {
   uint64_t pos = 0;
   int rc = hbam_reader_position(CTX(h), (uint64_t)i, &pos);

@@ -2,9 +2,10 @@
 //
 // BAMInputFormat with split planning and record reading on the MI355X path
 // when hadoopbam.gpu.enable is true (INTEGRATION.md section 2).  Everything
-// else -- and bounded traversal (intervals, unmapped-only; BAMInputFormat.java:
-// 143-184, 532-680), which the GPU path does not cover -- stays the stock
-// BAMInputFormat.
+// else stays the stock BAMInputFormat, and so does split planning under
+// bounded traversal (intervals, unmapped-only; BAMInputFormat.java:143-184,
+// 532-680: host-side work on htsjdk's BAMIndex); the splits it plans are read
+// by GpuBAMRecordReader, which filters their records on the GPU.
 //
 //   getSplits(splits, cfg)   BAMInputFormat.getSplits (:222-260): per file,
 //       addIndexedSplits (.splitting-bai, :264-318), else with
@@ -39,7 +40,7 @@ public class GpuBAMInputFormat extends BAMInputFormat {
   public static final String GPU_ENABLE_PROPERTY = "hadoopbam.gpu.enable";
 
   static boolean gpuEnabled(Configuration conf) {
-    return conf.getBoolean(GPU_ENABLE_PROPERTY, false) && !isBoundedTraversal(conf) && nativeAvailable();
+    return conf.getBoolean(GPU_ENABLE_PROPERTY, false) && nativeAvailable();
   }
 
   /** libhbam and its JNI glue load (else the stock classes serve every file). */
@@ -63,7 +64,9 @@ public class GpuBAMInputFormat extends BAMInputFormat {
 
   @Override
   public List<InputSplit> getSplits(List<InputSplit> splits, Configuration cfg) throws IOException {
-    if (!gpuEnabled(cfg)) return super.getSplits(splits, cfg);
+    // bounded traversal: the stock planner (its filterByInterval attaches the
+    // interval file pointers GpuBAMRecordReader passes to the GPU)
+    if (!gpuEnabled(cfg) || isBoundedTraversal(cfg)) return super.getSplits(splits, cfg);
     final List<InputSplit> orig = removeIndexFiles(splits);
     // as the reference: sorted by path, each file's splits handled together
     Collections.sort(orig, (a, b) -> ((FileSplit) a).getPath().compareTo(((FileSplit) b).getPath()));

@@ -22,23 +22,39 @@
 // that also carry their SAMRecordWritable.write bytes, encoded per batch on
 // the GPU (hbam_encode_writables).
 //
-// Bounded traversal (intervals / unmapped-only, BAMRecordReader.java:170-178)
-// is outside the GPU path: such splits are read by the stock BAMRecordReader
-// (GpuBAMInputFormat.createRecordReader).
+// Bounded traversal (hadoopbam.bam.intervals / hadoopbam.bam.bounded-traversal,
+// BAMRecordReader.java:170-178) is read on the GPU too: the split's chunk list
+// (FileVirtualSplit.getIntervalFilePointers, planned by the stock
+// BAMInputFormat.filterByInterval) and the optimized intervals go to
+// hbam_query_intervals, an unmapped-only split to hbam_query_unmapped, and
+// the record filter of htsjdk's index iterators runs on the device
+// (hbam_query_next).  Such values are built by the plain path (no per-batch
+// writable bytes), and getProgress works from the compressed offset of the
+// record last returned.
 //
 // Not compiled in this repository (no JDK in the build image); it binds the
 // native methods of HbamNative exactly as declared there.
 package org.seqdoop.hadoop_bam;
 
+import htsjdk.samtools.BAMIndex;
 import htsjdk.samtools.DefaultSAMRecordFactory;
+import htsjdk.samtools.QueryInterval;
 import htsjdk.samtools.SAMFileHeader;
 import htsjdk.samtools.SAMRecord;
 import htsjdk.samtools.SAMRecordFactory;
+import htsjdk.samtools.SamFiles;
+import htsjdk.samtools.SamInputResource;
+import htsjdk.samtools.SamReader;
+import htsjdk.samtools.SamReaderFactory;
 import htsjdk.samtools.ValidationStringency;
+import htsjdk.samtools.seekablestream.SeekableStream;
+import htsjdk.samtools.util.Interval;
 import java.io.IOException;
 import java.nio.ByteBuffer;
 import java.nio.ByteOrder;
+import java.util.List;
 import org.apache.hadoop.conf.Configuration;
+import org.apache.hadoop.fs.FileSystem;
 import org.apache.hadoop.fs.Path;
 import org.apache.hadoop.io.LongWritable;
 import org.apache.hadoop.mapreduce.InputSplit;
@@ -46,7 +62,9 @@ import org.apache.hadoop.mapreduce.RecordReader;
 import org.apache.hadoop.mapreduce.TaskAttemptContext;
 import org.seqdoop.hadoop_bam.gpu.HbamFiles;
 import org.seqdoop.hadoop_bam.gpu.HbamNative;
+import org.seqdoop.hadoop_bam.util.NIOFileUtil;
 import org.seqdoop.hadoop_bam.util.SAMHeaderReader;
+import org.seqdoop.hadoop_bam.util.WrapSeekable;
 
 public class GpuBAMRecordReader extends RecordReader<LongWritable, SAMRecordWritable> {
   /** Records per hbam_decode_span batch (hadoopbam.gpu.batch-records). */
@@ -77,6 +95,7 @@ public class GpuBAMRecordReader extends RecordReader<LongWritable, SAMRecordWrit
   private int n, i;  // records in the batch, next record to hand out
   private final long[] cursor = new long[1];
   private boolean started;  // a record has been handed out
+  private boolean bounded;  // bounded traversal: the batches come from an open query (queryNext)
 
   /** Device ordinal: hadoopbam.gpu.device, else LOCAL_RANK (one process per GPU), else 0. */
   static int device(Configuration conf) {
@@ -117,7 +136,10 @@ public class GpuBAMRecordReader extends RecordReader<LongWritable, SAMRecordWrit
     fileStart = virtualStart >>> 16;
     virtualEnd = split.getEndVirtualOffset();
     batchRecords = conf.getLong(BATCH_RECORDS_PROPERTY, 1L << 20);
-    encode = conf.getBoolean(GpuSAMRecordWritable.ENCODE_PROPERTY, false);
+    // as BAMRecordReader.initialize (:170): intervals, unmapped-only, or everything
+    bounded = BAMInputFormat.isBoundedTraversal(conf);
+    // query batches carry no writable bytes (hbam_encode_writables needs a split batch)
+    encode = !bounded && conf.getBoolean(GpuSAMRecordWritable.ENCODE_PROPERTY, false);
     record = encode ? new GpuSAMRecordWritable() : new SAMRecordWritable();
 
     // the file through its own file system, as WrapSeekable.openPath (:147):
@@ -130,14 +152,54 @@ public class GpuBAMRecordReader extends RecordReader<LongWritable, SAMRecordWrit
     cols = null;
     n = i = 0;
     started = false;
+    encoded = null;
+    if (bounded && split.getIntervalFilePointers() != null) {
+      // reads for intervals (:171-175): createIndexIterator(queryIntervals, false, filePointers)
+      final List<Interval> intervals = BAMInputFormat.getIntervals(conf);
+      final QueryInterval[] q = BAMInputFormat.prepareQueryIntervals(intervals, header.getSequenceDictionary());
+      final int[] iv = new int[3 * q.length];
+      for (int k = 0; k < q.length; ++k) {
+        iv[3 * k] = q[k].referenceIndex;
+        iv[3 * k + 1] = q[k].start;
+        iv[3 * k + 2] = q[k].end;
+      }
+      HbamNative.queryIntervals(ctx, iv, split.getIntervalFilePointers());
+    } else if (bounded) {
+      // unmapped reads (:176-178): queryUnmapped()
+      HbamNative.queryUnmapped(ctx, startOfUnmappedReads(path, conf));
+    }
     // htsjdk's iterator reads the first record when it is created
     // (bamFileReader.getIterator, :181-182): so does the first batch here,
     // and a first record that fails validation throws from initialize too
     nextBatch();
   }
 
+  /**
+   * Where htsjdk's queryUnmapped() starts reading: the file's index gives
+   * getStartOfLastLinearBin(); -1 (no linear entry at all) means the first
+   * record.  The index is found and opened as BAMRecordReader.initialize does
+   * (:144-148); without one htsjdk's getIndex() throws, as there.
+   */
+  private long startOfUnmappedReads(Path path, Configuration conf) throws IOException {
+    final FileSystem fs = path.getFileSystem(conf);
+    final java.nio.file.Path index = SamFiles.findIndex(NIOFileUtil.asPath(fs.makeQualified(path).toUri()));
+    final SeekableStream indexStream = index == null ? null : WrapSeekable.openPath(fs, new Path(index.toUri()));
+    SamInputResource resource = SamInputResource.of(WrapSeekable.openPath(fs, path));
+    if (indexStream != null) resource = resource.index(indexStream);
+    try (SamReader r = SamReaderFactory.makeDefault()
+                           .setOption(SamReaderFactory.Option.CACHE_FILE_BASED_INDEXES, true)
+                           .setUseAsyncIo(false)
+                           .validationStringency(stringency)
+                           .open(resource)) {
+      final BAMIndex idx = r.indexing().getIndex();
+      final long start = idx.getStartOfLastLinearBin();
+      return start != -1 ? start : HbamNative.header(ctx)[2];  // first_record_voff
+    }
+  }
+
   private void nextBatch() throws IOException {
-    cols = HbamNative.decodeSpan(ctx, cursor[0], virtualEnd, batchRecords, cursor);
+    cols = bounded ? HbamNative.queryNext(ctx, batchRecords)
+                   : HbamNative.decodeSpan(ctx, cursor[0], virtualEnd, batchRecords, cursor);
     for (ByteBuffer b : cols) b.order(ByteOrder.LITTLE_ENDIAN);
     n = cols[HbamNative.KEY].capacity() / 8;
     i = 0;
@@ -164,9 +226,16 @@ public class GpuBAMRecordReader extends RecordReader<LongWritable, SAMRecordWrit
   public float getProgress() throws IOException {
     if (reachedEnd) return 1;
     if (n == 0) return 0;  // an empty split before nextKeyValue has seen its end
+    final long fileEnd = virtualEnd >>> 16;
+    if (bounded) {
+      // no stream position of a read-ahead iterator here: the block of the record last returned
+      if (!started) return 0;
+      final long at = cols[HbamNative.VOFF].getLong(8 * (i - 1)) >>> 16;
+      final float p = (float) (at - fileStart) / (fileEnd - fileStart + 1);
+      return Math.max(0f, Math.min(1f, p));  // (an unmapped-only read ignores the split's bounds)
+    }
     // i - 1: the record nextKeyValue returned last; -1 (UINT64_MAX): none yet
     final long filePos = HbamNative.readerPosition(ctx, started ? i - 1 : -1L);
-    final long fileEnd = virtualEnd >>> 16;
     return (float) (filePos - fileStart) / (fileEnd - fileStart + 1);
   }
 
@@ -185,7 +254,7 @@ public class GpuBAMRecordReader extends RecordReader<LongWritable, SAMRecordWrit
   public boolean nextKeyValue() throws IOException {
     if (reachedEnd) return false;
     if (i == n) {
-      if (n == 0 || cursor[0] >= virtualEnd) {  // the split is done
+      if (n == 0 || (!bounded && cursor[0] >= virtualEnd)) {  // the split is done
         reachedEnd = true;
         return false;
       }

@@ -10,6 +10,8 @@
 //       (BAMRecordReader.java:123-184, 223-232, 209-219)  -> open, decodeSpan, readerPosition
 //       (the delegating classes: ../GpuBAMRecordReader.java, ../GpuBAMInputFormat.java,
 //        ../GpuSplittingBAMIndexer.java)
+//   BAMRecordReader.initialize's bounded branches (:170-178: createIndexIterator,
+//       queryUnmapped)                                    -> queryIntervals, queryUnmapped, queryNext
 //   SplittingBAMIndexer.index (SplittingBAMIndexer.java:248-290) -> splittingIndex
 //   SplittingBAMIndexer.processAlignment + finish (:186-202, 240-243)
 //       (write time, BAMRecordWriter.java:131-149)       -> splittingIndexForRecords
@@ -108,6 +110,31 @@ public final class HbamNative {
    */
   public static native ByteBuffer[] decodeSpan(long ctx, long vStart, long vEnd, long maxRecords, long[] cursor)
       throws IOException;
+
+  /**
+   * hbam_query_intervals: bamFileReader.createIndexIterator(queryIntervals,
+   * false, filePointers) (BAMRecordReader.java:171-175).  intervals = the
+   * optimized QueryIntervals as {referenceIndex, start, end} triples;
+   * filePointers = FileVirtualSplit.getIntervalFilePointers().  Opens the
+   * query {@link #queryNext} reads; IllegalArgumentException for intervals
+   * that are not optimized or chunks out of order.
+   */
+  public static native void queryIntervals(long ctx, int[] intervals, long[] filePointers) throws IOException;
+
+  /**
+   * hbam_query_unmapped: bamFileReader.queryUnmapped() (BAMRecordReader.java:
+   * 176-178) reading from startVoff (getIndex().getStartOfLastLinearBin(), or
+   * the first record's offset when that is -1).
+   */
+  public static native void queryUnmapped(long ctx, long startVoff) throws IOException;
+
+  /**
+   * hbam_query_next: the next records of the open query, at most maxRecords,
+   * as {@link #decodeSpan} returns a batch; no record: the end.  Records
+   * before a record that fails validation are delivered; the exception is
+   * thrown on the following call.
+   */
+  public static native ByteBuffer[] queryNext(long ctx, long maxRecords) throws IOException;
 
   /**
    * hbam_reader_position: BAMRecordReader.getProgress's in.position() after
