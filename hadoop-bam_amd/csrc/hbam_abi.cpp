@@ -608,6 +608,56 @@ int hbam_build_splitting_index(hbam_ctx* ctx, int32_t granularity, uint8_t** buf
   return HBAM_OK;
 }
 
+int hbam_build_bai(hbam_ctx* ctx, int32_t flags, uint8_t** buf, uint64_t* len) {
+  *buf = nullptr;
+  *len = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  if (!ctx->f->is_bam()) {
+    ctx->err = "hbam_build_bai needs a BAM (the ctx was opened as plain BGZF)";
+    return HBAM_E_STATE;
+  }
+  reset_cursors(ctx);
+  std::vector<uint8_t> out;
+  hadoop_bam::BaiBuilder b;
+  const int rc = b.build(*ctx->f, (flags & HBAM_BAI_METADATA) != 0, &out, &ctx->err);
+  if (rc != HBAM_OK) return rc;
+  *buf = static_cast<uint8_t*>(malloc(out.size() ? out.size() : 1));
+  if (!*buf) return HBAM_E_NOMEM;
+  memcpy(*buf, out.data(), out.size());
+  *len = out.size();
+  return HBAM_OK;
+}
+
+int hbam_bai_summarize(const void* bai, uint64_t len, hbam_bai_summary* out) {
+  memset(out, 0, sizeof *out);
+  out->start_of_last_linear_bin = -1;
+  hadoop_bam::BaiIndex idx;
+  const int rc = idx.parse(static_cast<const uint8_t*>(bai), len, &g_open_err);
+  if (rc != HBAM_OK) return rc;
+  out->n_ref = (int32_t)idx.refs.size();
+  out->has_no_coor = idx.has_no_coor ? 1 : 0;
+  out->no_coor_count = idx.no_coor;
+  out->start_of_last_linear_bin = idx.start_of_last_linear_bin();
+  return HBAM_OK;
+}
+
+int hbam_bai_query(const void* bai, uint64_t len, const hbam_interval* iv, uint64_t n_iv, uint64_t** file_pointers,
+                   uint64_t* n_ptrs) {
+  *file_pointers = nullptr;
+  *n_ptrs = 0;
+  hadoop_bam::BaiIndex idx;
+  int rc = idx.parse(static_cast<const uint8_t*>(bai), len, &g_open_err);
+  if (rc != HBAM_OK) return rc;
+  std::vector<uint64_t> out;
+  rc = idx.query(reinterpret_cast<const hadoop_bam::QueryInterval*>(iv), n_iv, &out, &g_open_err);
+  if (rc != HBAM_OK) return rc;
+  *file_pointers = static_cast<uint64_t*>(malloc(out.empty() ? 8 : out.size() * 8));
+  if (!*file_pointers) return HBAM_E_NOMEM;
+  if (!out.empty()) memcpy(*file_pointers, out.data(), out.size() * 8);
+  *n_ptrs = out.size();
+  return HBAM_OK;
+}
+
 int hbam_splitting_entries(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_t granularity, uint64_t ordinal0,
                            uint64_t** entries, uint64_t* n_entries, uint64_t* n_records) {
   *entries = nullptr;

@@ -174,6 +174,7 @@ int BamFile::init(const OpenOptions& o, std::string* err) {
   set_window_bytes(o.window_bytes ? o.window_bytes : kDefaultWindowBytes);
   window_explicit_ = o.window_bytes != 0;
   int rc;
+  is_bam_ = o.parse_header;
   if (o.parse_header) {
     rc = parse_header();
   } else {  // plain BGZF: the first window's framing is checked at open
@@ -769,43 +770,15 @@ int BAMInputFormat::addProbabilisticSplits(BamFile& f, const std::vector<FileSpl
 // ---------------------------------------------------------------------------
 int LinearBAMIndex::read(const uint8_t* d, uint64_t len, std::string* err) {
   lin_.clear();
-  uint64_t p = 0;
-  auto need = [&](uint64_t k) { return p + k <= len; };
-  auto i32 = [&]() {
-    const int32_t v = rd_i32(d + p);
-    p += 4;
-    return v;
-  };
-  if (!need(8) || memcmp(d, "BAI\1", 4) != 0) {
-    *err = "Invalid file header in BAM index";
-    return kErrIO;
-  }
-  p = 4;
-  const int32_t n_ref = i32();
-  if (n_ref < 0) {
-    *err = "Invalid BAM index: negative reference count";
-    return kErrIO;
-  }
-  lin_.resize((size_t)n_ref);
-  for (int32_t r = 0; r < n_ref; ++r) {
-    if (!need(4)) { *err = "Premature end of BAM index"; return kErrIO; }
-    const int32_t n_bin = i32();
-    for (int32_t b = 0; b < n_bin; ++b) {
-      if (!need(8)) { *err = "Premature end of BAM index"; return kErrIO; }
-      p += 4;
-      const int32_t n_chunk = i32();
-      if (n_chunk < 0 || !need(16ull * (uint64_t)n_chunk)) { *err = "Premature end of BAM index"; return kErrIO; }
-      p += 16ull * (uint64_t)n_chunk;
+  BaiIndex idx;  // (the pseudo-bins and the trailing n_no_coor of an index with metadata parse like any other)
+  if (idx.parse(d, len, err) != kOk) return kErrIO;
+  lin_.resize(idx.refs.size());
+  for (size_t r = 0; r < idx.refs.size(); ++r) {
+    const BaiIndex::Ref& ref = idx.refs[r];
+    if (ref.n_bin > 0) {
+      lin_[r].resize((size_t)ref.n_intv);
+      for (int32_t k = 0; k < ref.n_intv; ++k) lin_[r][(size_t)k] = idx.lin_at(ref, k);
     }
-    if (!need(4)) { *err = "Premature end of BAM index"; return kErrIO; }
-    const int32_t n_intv = i32();
-    if (n_intv < 0 || !need(8ull * (uint64_t)n_intv)) { *err = "Premature end of BAM index"; return kErrIO; }
-    if (n_bin > 0) {
-      auto& v = lin_[(size_t)r];
-      v.resize((size_t)n_intv);
-      for (int32_t k = 0; k < n_intv; ++k) memcpy(&v[(size_t)k], d + p + 8ull * (uint64_t)k, 8);
-    }
-    p += 8ull * (uint64_t)n_intv;
   }
   return kOk;
 }

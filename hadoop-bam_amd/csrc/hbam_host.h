@@ -134,6 +134,7 @@ class BamFile {
   const std::vector<std::string>& ref_names() const { return ref_names_; }
   const std::vector<int32_t>& ref_lens() const { return ref_lens_; }
   uint64_t first_record_voff() const { return first_voff_; }
+  bool is_bam() const { return is_bam_; }  // opened with its BAM header parsed (not hbam_open_bgzf)
 
   std::string& error() { return err_; }
 
@@ -179,6 +180,7 @@ class BamFile {
   bool win_free_ = false;
   uint64_t window_bytes_ = kDefaultWindowBytes;
   bool window_explicit_ = false;
+  bool is_bam_ = false;
   int32_t n_ref_ = 0;
   std::string text_;
   std::vector<std::string> ref_names_;
@@ -510,6 +512,61 @@ class QueryCursor {
   hbam::DevBuf<uint32_t> p_, idx_, flag_, slot_;
   hbam::DevBuf<uint64_t> klen_, roff_, src_off_, state_;
   hbam::DevBuf<uint8_t> tmp_, cols_, rests_;
+};
+
+// A parsed .bai (SAM spec 5.2): per contig where its bins and its linear index
+// lie in the bytes, and the optional trailing n_no_coor.  The one parser of
+// the split planner (LinearBAMIndex) and of hbam_bai_summarize / hbam_bai_query.
+struct BaiIndex {
+  struct Ref {
+    uint64_t bins = 0;  // offset of the first bin
+    int32_t n_bin = 0;
+    uint64_t lin = 0;   // offset of the first linear entry
+    int32_t n_intv = 0;
+  };
+  const uint8_t* d = nullptr;
+  std::vector<Ref> refs;
+  bool has_no_coor = false;
+  uint64_t no_coor = 0;
+  // kErrFormat with the reader's message in *err
+  int parse(const uint8_t* data, uint64_t len, std::string* err);
+  uint64_t lin_at(const Ref& r, int32_t w) const;
+  // getStartOfLastLinearBin: -1 when no contig has a linear index
+  int64_t start_of_last_linear_bin() const;
+  // the chunk list of optimized intervals (hbam_bai_query): flat pairs, ascending
+  int query(const QueryInterval* iv, uint64_t n_iv, std::vector<uint64_t>* out, std::string* err) const;
+};
+// [htsjdk] assertIntervalsOptimized (+ no interval ending more than one base
+// before its start): kErrArg with the message in *err
+int check_intervals_optimized(const QueryInterval* iv, uint64_t n_iv, std::string* err);
+
+// The .bai of a file being built (hbam_build_bai): the file's records are
+// decoded window by window (BamFile::decode_step from the first record) and
+// each window's records go through the kernels of hbam_bai.h.  Across windows
+// live, on the device, the linear tables, the per-contig 0x4 counts and the run
+// list (the chunks in file order), and on the host the last record's key, the
+// largest sort key so far and the record ordinal; the run a window leaves open
+// is closed by the next window's first boundary, or at the end of the file.
+class BaiBuilder {
+ public:
+  BaiBuilder() = default;
+  BaiBuilder(const BaiBuilder&) = delete;
+  BaiBuilder& operator=(const BaiBuilder&) = delete;
+  // the whole index; metadata: the pseudo-bins and n_no_coor
+  int build(BamFile& f, bool metadata, std::vector<uint8_t>* out, std::string* err);
+
+ private:
+  int begin(BamFile& f, bool metadata, std::string* err);
+  int add_window(BamFile& f, const SpanDev& s, std::string* err);
+  int finish(BamFile& f, std::vector<uint8_t>* out, std::string* err);
+
+  std::vector<uint32_t> lin_off_;  // n_ref + 1: the contigs' first windows
+  uint64_t carry_key_ = 0, carry_sk_ = 0, records_ = 0, runs_ = 0;
+  bool metadata_ = false;          // count the placed unmapped records per contig
+  hbam::DevBuf<uint32_t> d_lin_off_, bflag_, slot_, iota_, perm_, ord_, last_;
+  hbam::DevBuf<uint64_t> lin_, unm_, state_, key_, sk_, skmax_, wspan_, run_key_, run_start_, run_end_, run_ord_,
+      s_key_, s_start_, s_end_, s_count_, filled_;
+  hbam::DevBuf<uint8_t> tmp_;
 };
 
 // BAMRecordReader (BAMRecordReader.java:63-233) over one FileVirtualSplit.

@@ -56,18 +56,16 @@ int QueryCursor::begin(BamFile& f, std::string* err) {
   return kOk;
 }
 
-int QueryCursor::open_intervals(BamFile& f, const QueryInterval* iv, uint64_t n_iv, const uint64_t* ptrs,
-                                uint64_t n_ptrs, std::string* err) {
+int check_intervals_optimized(const QueryInterval* iv, uint64_t n_iv, std::string* err) {
   if (n_iv >= (1ull << 31)) {
     *err = "too many intervals";
     return kErrArg;
   }
   // [htsjdk] assertIntervalsOptimized: sorted, and neither overlapping nor abutting
-  std::vector<int32_t> h(3 * n_iv);  // ref | start | effective end
   for (uint64_t k = 0; k < n_iv; ++k) {
     const int32_t end = iv[k].end <= 0 ? INT32_MAX : iv[k].end;
     if (k) {
-      const int32_t pend = h[2 * n_iv + k - 1];
+      const int32_t pend = iv[k - 1].end <= 0 ? INT32_MAX : iv[k - 1].end;
       if (iv[k].ref_id < iv[k - 1].ref_id || (iv[k].ref_id == iv[k - 1].ref_id && iv[k].start <= pend)) {
         *err = "query intervals are not optimized: sort them and merge overlapping ones";
         return kErrArg;
@@ -79,9 +77,19 @@ int QueryCursor::open_intervals(BamFile& f, const QueryInterval* iv, uint64_t n_
       *err = "query interval ends before it starts";
       return kErrArg;
     }
+  }
+  return kOk;
+}
+
+int QueryCursor::open_intervals(BamFile& f, const QueryInterval* iv, uint64_t n_iv, const uint64_t* ptrs,
+                                uint64_t n_ptrs, std::string* err) {
+  int rc = check_intervals_optimized(iv, n_iv, err);
+  if (rc != kOk) return rc;
+  std::vector<int32_t> h(3 * n_iv);  // ref | start | effective end
+  for (uint64_t k = 0; k < n_iv; ++k) {
     h[k] = iv[k].ref_id;
     h[n_iv + k] = iv[k].start;
-    h[2 * n_iv + k] = end;
+    h[2 * n_iv + k] = iv[k].end <= 0 ? INT32_MAX : iv[k].end;
   }
   if (n_ptrs & 1) {
     *err = "file pointers come in pairs (chunk start, chunk end)";
@@ -95,8 +103,7 @@ int QueryCursor::open_intervals(BamFile& f, const QueryInterval* iv, uint64_t n_
     }
     chunks_.emplace_back(ptrs[k], ptrs[k + 1]);
   }
-  int rc = begin(f, err);
-  if (rc != kOk) return rc;
+  if ((rc = begin(f, err)) != kOk) return rc;
   unmapped_ = false;
   n_iv_ = (uint32_t)n_iv;
   if (n_iv) {

@@ -56,6 +56,10 @@ class Batch(C.Structure):
                                                             ("next_voff", u64)]
 
 
+class BaiSummary(C.Structure):
+    _fields_ = [("n_ref", i32), ("has_no_coor", i32), ("start_of_last_linear_bin", i64), ("no_coor_count", u64)]
+
+
 class GpuStats(C.Structure):
     _fields_ = [("n_blocks", u64), ("compressed_bytes", u64), ("inflated_bytes", u64), ("records", u64),
                 ("first_voff", u64), ("last_voff", u64), ("key_xor", u64), ("voff_sum", u64),
@@ -99,6 +103,7 @@ _sig("hbam_bytes_read", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_prefetch", C.c_int, [P, u64, u64])
 _sig("hbam_splitting_index_for_records", C.c_int, [C.POINTER(Opts), P, u64, i32, u64, C.POINTER(P), C.POINTER(u64)])
 _sig("hbam_build_splitting_index", C.c_int, [P, i32, C.POINTER(P), C.POINTER(u64)])
+_sig("hbam_build_bai", C.c_int, [P, i32, C.POINTER(P), C.POINTER(u64)])
 _sig("hbam_splitting_entries", C.c_int, [P, u64, u64, i32, u64, C.POINTER(P), C.POINTER(u64), C.POINTER(u64)])
 _sig("hbam_guess_record_starts", C.c_int, [P, P, P, u64, P])
 _sig("hbam_guess_record_starts_hdr", C.c_int, [P, i32, P, P, u64, P])
@@ -132,8 +137,11 @@ _sig("hbam_gpu_d2d_bandwidth", C.c_int, [P, u64, i32, C.POINTER(C.c_float)])
 _sig("hbam_bgzf_compress", C.c_int, [C.POINTER(Opts), P, u64, P, u64, i32, i32, i32, C.POINTER(P), C.POINTER(u64)])
 _sig("hbam_gpu_bgzf_compress", C.c_int, [P, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_fetch_compressed", C.c_int, [P, u64, u64, P])
+_sig("hbam_bai_summarize", C.c_int, [P, u64, C.POINTER(BaiSummary)])
+_sig("hbam_bai_query", C.c_int, [P, u64, P, u64, C.POINTER(P), C.POINTER(u64)])
 
 BGZF_EOF = 1
+BAI_METADATA = 1  # hbam_build_bai: the pseudo-bins 37450 and the trailing n_no_coor
 HTSJDK_BLOCK_SIZE = 65498  # ISIZE of every full block of test.bam (htsjdk-written)
 
 
@@ -219,6 +227,35 @@ def splitting_index_for_records(voffs, granularity, file_size, device=0) -> byte
         raise HbamError(rc, _L.hbam_last_error(None).decode())
     try:
         return C.string_at(out, n.value)
+    finally:
+        _L.hbam_free(out)
+
+
+def bai_summary(bai: bytes):
+    """hbam_bai_summarize of a .bai's bytes (host code, no GPU): n_ref,
+    has_no_coor, start_of_last_linear_bin (what query_unmapped reads from; -1:
+    no linear index) and no_coor_count."""
+    st = BaiSummary()
+    rc = _L.hbam_bai_summarize(C.c_char_p(bytes(bai)), len(bai), C.byref(st))
+    if rc != OK:
+        raise HbamError(rc, _L.hbam_last_error(None).decode(errors="replace"))
+    return {"n_ref": st.n_ref, "has_no_coor": bool(st.has_no_coor),
+            "start_of_last_linear_bin": st.start_of_last_linear_bin, "no_coor_count": st.no_coor_count}
+
+
+def bai_query(bai: bytes, intervals):
+    """hbam_bai_query (host code, no GPU): the file pointers of optimized
+    intervals [(ref_id, start, end)] in a .bai -- the flat chunk list
+    [s0, e0, s1, e1, ...] BamFile.query_intervals takes."""
+    iv = np.ascontiguousarray(np.asarray(intervals, np.int32).reshape(-1, 3))
+    out = P()
+    n = u64()
+    rc = _L.hbam_bai_query(C.c_char_p(bytes(bai)), len(bai), iv.ctypes.data if len(iv) else None, len(iv),
+                           C.byref(out), C.byref(n))
+    if rc != OK:
+        raise HbamError(rc, _L.hbam_last_error(None).decode(errors="replace"))
+    try:
+        return [int(x) for x in np.frombuffer(C.string_at(out, 8 * n.value), np.uint64)]
     finally:
         _L.hbam_free(out)
 
@@ -569,6 +606,19 @@ class BamFile:
         b = C.string_at(p, n.value)
         _L.hbam_free(p)
         return b
+
+    def build_bai(self, metadata=True) -> bytes:
+        """The file's .bai computed on the GPU (hbam_build_bai); metadata: with
+        the per-contig pseudo-bins 37450 and the trailing n_no_coor."""
+        p = P()
+        n = u64()
+        rc = _L.hbam_build_bai(self._h, BAI_METADATA if metadata else 0, C.byref(p), C.byref(n))
+        if rc != OK:
+            raise self._err(rc)
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            _L.hbam_free(p)
 
     def splitting_entries(self, vstart, vend, granularity, ordinal0):
         """This split's part of SplittingBAMIndexer.index (hbam_splitting_entries):

@@ -190,8 +190,8 @@ typedef struct hbam_interval { int32_t ref_id, start, end; } hbam_interval;
  * other call on the ctx that reads the file, since each of them moves the
  * ctx's window: hbam_decode_span*, hbam_decode_writables, hbam_prefetch,
  * hbam_file_stats, hbam_blocks, hbam_read_inflated,
- * hbam_build_splitting_index, hbam_splitting_entries, hbam_get_splits*,
- * hbam_guess_*.  hbam_header, hbam_ref, hbam_bytes_read,
+ * hbam_build_splitting_index, hbam_splitting_entries, hbam_build_bai,
+ * hbam_get_splits*, hbam_guess_*.  hbam_header, hbam_ref, hbam_bytes_read,
  * hbam_pipeline_counters and hbam_last_error leave it open. */
 int hbam_query_intervals(hbam_ctx *ctx, const hbam_interval *iv, uint64_t n_iv, const uint64_t *file_pointers,
                          uint64_t n_ptrs);
@@ -267,6 +267,67 @@ int hbam_get_splits(hbam_ctx *ctx, const uint64_t *starts, const uint64_t *lengt
 int hbam_get_splits_bai(hbam_ctx *ctx, const uint64_t *starts, const uint64_t *lengths, uint64_t n,
                         const uint8_t *sbi, uint64_t sbi_len, const uint8_t *bai, uint64_t bai_len,
                         uint64_t *vstarts, uint64_t *vends, uint64_t *nout);
+
+/* ---- the BAM index (.bai, SAM spec 5.2): built on the GPU, read on the host ---- */
+/* The .bai of a coordinate-sorted BAM, computed on the GPU: the file is
+ * streamed through HBM window by window from the first record to the end of
+ * the file (as hbam_build_splitting_index does), its records validated under
+ * the ctx's stringency, and per record the kernels compute
+ *   - whether it is indexed: refID >= 0 and pos >= 0 (the others only count
+ *     towards n_no_coor);
+ *   - its end: pos + 1 for a placed unmapped read (flag 0x4), else pos +
+ *     max(reference length of the CIGAR, 1) (M, D, N, = and X consume the
+ *     reference; the sum wraps as a Java int and the CIGAR is clipped to the
+ *     record, as in the bounded-traversal filter);
+ *   - its bin reg2bin(pos, end) -- computed, not the record's stored bin;
+ *   - the 16 kbp windows it touches: pos >> 14 .. (end - 1) >> 14, for a
+ *     placed unmapped read the single window max(pos - 1, 0) >> 14.
+ * Chunks: a record extends the last chunk of its (refID, bin) when the record
+ * before it in the file was indexed into the same (refID, bin), else it starts
+ * a chunk at its virtual offset; a chunk ends at the virtual offset of the
+ * record after its last record (file_size << 16 after the file's last
+ * record).  A bin's chunks are in file order, a contig's bins in ascending
+ * order.  Linear index: entry w = the smallest virtual offset among the
+ * records touching window w; an untouched window takes the last touched entry
+ * before it (0 if none); n_intv = the highest touched window + 1; a contig
+ * with no indexed record has n_bin = n_intv = 0.
+ * flags: HBAM_BAI_METADATA adds, per contig with an indexed record, a last
+ * bin 37450 with two chunks -- (offset of the contig's first indexed record,
+ * chunk end of its last one) and (indexed records without 0x4, with 0x4) --
+ * and, after the last contig, the u64 count of unindexed records.
+ * The index follows the SAM specification and this repository's oracle; it is
+ * a valid index for htsjdk and htslib readers, but byte equality with the file
+ * htsjdk's BAMIndexer writes (its chunk coalescing) is not claimed.
+ * HBAM_E_FORMAT: indexed records not in non-decreasing (refID, pos) order
+ * (the file is not coordinate-sorted); a record ending past 2^29; a record
+ * touching a window past (min(l_ref, 2^29) >> 14) + 1 windows of its contig
+ * (the tables are sized from the header); a refID past the header's contigs.
+ * HBAM_E_STATE on a ctx from hbam_open_bgzf or hbam_open_codec.  Ends an open
+ * query.  *buf released with hbam_free. */
+#define HBAM_BAI_METADATA 1   /* per-contig pseudo-bin 37450 + trailing n_no_coor (SAM spec 5.2) */
+int hbam_build_bai(hbam_ctx *ctx, int32_t flags, uint8_t **buf, uint64_t *len);
+
+/* Reading a .bai (host code: no device, no ctx; errors: hbam_last_error(NULL)). */
+typedef struct hbam_bai_summary {
+  int32_t n_ref, has_no_coor;
+  int64_t start_of_last_linear_bin;   /* [htsjdk] getStartOfLastLinearBin: last entry of the last contig with a linear index; -1 if none */
+  uint64_t no_coor_count;             /* trailing n_no_coor; 0 when absent */
+} hbam_bai_summary;
+/* A malformed index -> HBAM_E_FORMAT. */
+int hbam_bai_summarize(const void *bai, uint64_t len, hbam_bai_summary *out);
+/* The chunk side of BAMInputFormat.filterByInterval (BAMInputFormat.java:571-574):
+ * the file pointers hbam_query_intervals takes.  Per interval (1-based
+ * inclusive, end <= 0 = to the end of the reference): beg0 = max(start - 1, 0),
+ * end0 = end <= 0 ? 2^29 : end; every chunk of the bins reg2bins(beg0, end0)
+ * (never the pseudo-bin 37450) whose end lies above the linear entry of window
+ * beg0 >> 14 (past the table: its last entry; no linear index: 0); sorted, two
+ * chunks merged when start <= the previous end.  The result is the union over
+ * the intervals, sorted and merged again: n_ptrs / 2 pairs (start, end),
+ * ascending; *file_pointers released with hbam_free.  Intervals not optimized
+ * (the rule of hbam_query_intervals) or a ref_id outside [0, n_ref) ->
+ * HBAM_E_ARG; a malformed index -> HBAM_E_FORMAT. */
+int hbam_bai_query(const void *bai, uint64_t len, const hbam_interval *iv, uint64_t n_iv,
+                   uint64_t **file_pointers, uint64_t *n_ptrs);
 
 /* ---- SAMRecordWritable codec (map-output serialization for the shuffle) ---- */
 /* SAMRecordWritable.write (SAMRecordWritable.java:55-64) of every record of

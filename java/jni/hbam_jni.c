@@ -299,6 +299,60 @@ JNIEXPORT jbyteArray FN(splittingIndex)(JNIEnv *env, jclass c, jlong h, jint g) 
   return a;
 }
 
+JNIEXPORT jbyteArray FN(buildBai)(JNIEnv *env, jclass c, jlong h, jboolean metadata) {
+  uint8_t *buf = NULL;
+  uint64_t len = 0;
+  int rc = hbam_build_bai(CTX(h), metadata ? HBAM_BAI_METADATA : 0, &buf, &len);
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, hbam_last_error(CTX(h)));
+    return NULL;
+  }
+  jbyteArray a = to_bytes(env, buf, len);
+  hbam_free(buf);
+  return a;
+}
+
+/* {n_ref, has_no_coor, start_of_last_linear_bin, no_coor_count} */
+JNIEXPORT jlongArray FN(baiSummary)(JNIEnv *env, jclass c, jbyteArray bai) {
+  const jsize n = bai ? (*env)->GetArrayLength(env, bai) : 0;
+  jbyte *b = n ? (*env)->GetByteArrayElements(env, bai, NULL) : NULL;
+  hbam_bai_summary s;
+  int rc = n && !b ? HBAM_E_NOMEM : hbam_bai_summarize(b, (uint64_t)n, &s);
+  if (b) (*env)->ReleaseByteArrayElements(env, bai, b, JNI_ABORT);
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, hbam_last_error(NULL));
+    return NULL;
+  }
+  const uint64_t v[4] = {(uint64_t)s.n_ref, (uint64_t)s.has_no_coor, (uint64_t)s.start_of_last_linear_bin,
+                         s.no_coor_count};
+  return to_longs(env, v, 4);
+}
+
+/* intervals: {ref_id, start, end} triples; returns the file pointers (chunk start, chunk end, ...) */
+JNIEXPORT jlongArray FN(baiQuery)(JNIEnv *env, jclass c, jbyteArray bai, jintArray intervals) {
+  const jsize ni = intervals ? (*env)->GetArrayLength(env, intervals) : 0;
+  if (ni % 3) {
+    throw_for(env, HBAM_E_ARG, "intervals are (ref, start, end) triples");
+    return NULL;
+  }
+  const jsize n = bai ? (*env)->GetArrayLength(env, bai) : 0;
+  jbyte *b = n ? (*env)->GetByteArrayElements(env, bai, NULL) : NULL;
+  jint *iv = ni ? (*env)->GetIntArrayElements(env, intervals, NULL) : NULL;
+  uint64_t *fp = NULL, np = 0;
+  int rc = (n && !b) || (ni && !iv) ? HBAM_E_NOMEM
+                                    : hbam_bai_query(b, (uint64_t)n, (const hbam_interval *)iv, (uint64_t)(ni / 3),
+                                                     &fp, &np);
+  if (iv) (*env)->ReleaseIntArrayElements(env, intervals, iv, JNI_ABORT);
+  if (b) (*env)->ReleaseByteArrayElements(env, bai, b, JNI_ABORT);
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, hbam_last_error(NULL));
+    return NULL;
+  }
+  jlongArray a = to_longs(env, fp, (jsize)np);
+  hbam_free(fp);
+  return a;
+}
+
 JNIEXPORT jbyteArray FN(splittingIndexForRecords)(JNIEnv *env, jclass c, jint device, jlongArray voffs, jint g,
                                                   jlong file_size) {
   jsize n;

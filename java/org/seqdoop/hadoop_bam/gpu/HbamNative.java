@@ -146,6 +146,27 @@ public final class HbamNative {
   public static native byte[] splittingIndex(long ctx, int granularity) throws IOException;
 
   /**
+   * hbam_build_bai: the file's .bai (SAM spec 5.2) computed on the GPU, the
+   * file streamed window by window; metadata adds the per-contig pseudo-bins
+   * 37450 and the trailing count of records without coordinates.
+   * SAMFormatException for a file that is not coordinate-sorted.
+   */
+  public static native byte[] buildBai(long ctx, boolean metadata) throws IOException;
+
+  /**
+   * hbam_bai_summarize (host code, no ctx): {n_ref, has_no_coor,
+   * getStartOfLastLinearBin() or -1, n_no_coor} of a .bai's bytes.
+   */
+  public static native long[] baiSummary(byte[] bai) throws IOException;
+
+  /**
+   * hbam_bai_query (host code, no ctx): the file pointers {start0, end0, ...}
+   * of optimized intervals ({referenceIndex, start, end} triples) in a .bai,
+   * as {@link #queryIntervals} takes them.
+   */
+  public static native long[] baiQuery(byte[] bai, int[] intervals) throws IOException;
+
+  /**
    * hbam_splitting_index_for_records: the write-time index of a written file:
    * processAlignment for records at voffs (file order), then finish(fileSize).
    */
