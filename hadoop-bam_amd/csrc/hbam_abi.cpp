@@ -488,6 +488,12 @@ int hbam_inflate_token_count(hbam_ctx* ctx, uint64_t* tokens) {
   return ctx->f->pipe().inflate_tokens(tokens) == 0 ? HBAM_OK : HBAM_E_DEVICE;
 }
 
+int hbam_inflate_path_counts(hbam_ctx* ctx, uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  return ctx->f->pipe().inflate_path_counts(out) == 0 ? HBAM_OK : HBAM_E_DEVICE;
+}
+
 int hbam_decode_span_device(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_t flags, hbam_gpu_stats* st) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   reset_cursors(ctx);

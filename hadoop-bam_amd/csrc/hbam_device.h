@@ -71,6 +71,25 @@ struct HuffTableInfo {
   uint32_t est_bits;   // expected compressed bits of that block (block_bits_estimate)
 };
 
+// Phase A's two paths.  Each round the lean launch (k_inflate_huff) hands the
+// blocks it does not handle to k_huff_fallback through a per-chunk device
+// list of u32: [r] = blocks handed over in round r (zeroed on the stream
+// before the chunk's first round), [kHuffListHdr + i] = the i-th one's index
+// in the chunk.
+constexpr uint32_t kHuffListHdr = 8;
+static_assert(kInflateRounds <= kHuffListHdr, "one list counter per round");
+// the fallback's grid: it strides over the list (an empty list costs one
+// small launch, not the ~47 us of a near-empty launch over the chunk)
+constexpr uint32_t kHuffFallbackGrid = 1024;
+// Path counters of the last inflate (u32 words, read only on request):
+// block rounds the fallback decoded, and those the lean instance completed,
+// spread over kPathStatSlots words in separate 128 B lines.
+constexpr uint32_t kPathStatFallback = 0;
+constexpr uint32_t kPathStatLean = 32;
+constexpr uint32_t kPathStatSlots = 16;
+constexpr uint32_t kPathStatStride = 32;
+constexpr uint32_t kPathStatWords = kPathStatLean + kPathStatSlots * kPathStatStride;
+
 // Record-chain transition rules.
 enum ChainMode : int {
   kReader = 0,  // [htsjdk] BAMRecordCodec.decode (BAMRecordReader path)

@@ -315,14 +315,22 @@ __global__ void k_block_ustart(BlockInfo* __restrict__ blocks, uint32_t n, const
 #endif
 constexpr int kHuffThreads = HBAM_HUFF_THREADS;  // lanes per DEFLATE block (a multiple of 64)
 constexpr int kHuffWaves = kHuffThreads / 64;
-// Phase A reads the compressed block from an LDS copy (staged) or straight
-// from HBM/L2, per chunk: staged while the workgroup's LDS (tables + the
-// chunk's largest block) leaves room for 4 workgroups per CU, else unstaged
-// (C4: 7.4 -> 3.9 ms; C2: staged 7.6 vs 8.0 ms).
+// Phase A runs as two kernels per round.  The lean instance (k_inflate_huff)
+// decodes one DEFLATE block per workgroup from prebuilt tables, with only the
+// round's window of compressed bits staged in LDS, at kLeanWavesPerSimd waves
+// per SIMD; whatever it does not handle goes to the fallback kernel
+// (k_huff_fallback), the full body (huff_block) at 4 waves per SIMD, which
+// reads the block from an LDS copy (staged) when the tables + the block fit
+// kHuffStageMaxLds, else straight from HBM/L2 (C4: 7.4 -> 3.9 ms; C2: staged
+// 7.6 vs 8.0 ms).
+// HBAM_HUFF_STAGE_MAX / HBAM_HUFF_WAVES_PER_SIMD: the lean instance's LDS per
+// workgroup and its waves per SIMD (A/B knobs; 40 KB and 4 = the fallback's
+// own, fixed, geometry).
 #ifndef HBAM_HUFF_STAGE_MAX
-#define HBAM_HUFF_STAGE_MAX (40 * 1024)
+#define HBAM_HUFF_STAGE_MAX (32 * 1024)
 #endif
-constexpr uint32_t kHuffStageMaxLds = HBAM_HUFF_STAGE_MAX;
+constexpr uint32_t kLeanLds = HBAM_HUFF_STAGE_MAX;
+constexpr uint32_t kHuffStageMaxLds = 40 * 1024;
 
 // Wave-local ordering of LDS traffic (code run by one wave only).
 __device__ __forceinline__ void wave_sync() {
@@ -780,7 +788,11 @@ __device__ __forceinline__ uint32_t dist_lookup(const HuffLds& L, uint64_t b) {
 
 // lane_decode exit events (EV_MERGE: the sync walk reached a boundary of the
 // lane's speculative walk)
-enum : uint32_t { EV_STOP = 0, EV_EOB = 1, EV_INPUT = 2, EV_ERR = 3, EV_FULLX = 4, EV_FULLO = 5, EV_MERGE = 6 };
+// (EV_HAND, lean instance only: the symbol needs the canonical decode, which
+// the lean instance leaves to the fallback kernel)
+enum : uint32_t {
+  EV_STOP = 0, EV_EOB = 1, EV_INPUT = 2, EV_ERR = 3, EV_FULLX = 4, EV_FULLO = 5, EV_MERGE = 6, EV_HAND = 7
+};
 enum { LD_SPEC = 0, LD_SYNC = 1, LD_EMIT = 2 };
 
 // Boundaries of a lane's speculative walk: p[k] = bit position after symbol
@@ -800,6 +812,9 @@ constexpr uint32_t kMergeShortBits = HBAM_MERGE_SHORT_BITS;
 #define HBAM_MERGE_TINY_BITS 0
 #endif
 constexpr uint32_t kMergeTinyBits = HBAM_MERGE_TINY_BITS;  // ... kMergeFirst / 4 << k below this
+// (the first boundary of a short / tiny slice, kMergeFirst / 2 or / 4, is at least one symbol)
+static_assert(kMergeShortBits == 0 || kMergeFirst >= 2, "kMergeShortBits needs kMergeFirst >= 2");
+static_assert(kMergeTinyBits == 0 || kMergeFirst >= 4, "kMergeTinyBits needs kMergeFirst >= 4");
 struct MergePts {
   uint32_t p0, p1, p2, p3;
   uint32_t b0, b1, b2, b3;
@@ -818,7 +833,9 @@ struct __attribute__((packed, aligned(4))) Tok4 {
 //   LD_SYNC stops with EV_MERGE (mj = index) when it reaches one of them;
 //   LD_EMIT writes tokens to tok[0..nt) and applies the output-space rules with
 //           the output position of the first token = out0.
-template <int MODE>
+// LEAN: L holds the four decode tables only (no cnt_* / sort_*): a symbol that
+// needs the canonical decode ends the walk with EV_HAND.
+template <int MODE, bool LEAN = false>
 __device__ __forceinline__ uint32_t lane_decode(const HuffLds& L, const uint32_t* __restrict__ W, uint32_t a,
                                                 uint32_t stop, uint32_t E, uint32_t& x, uint32_t& nt, uint32_t& nb,
                                                 MergePts& mp, uint32_t& mj, uint32_t* __restrict__ tok,
@@ -1012,12 +1029,24 @@ __device__ __forceinline__ uint32_t lane_decode(const HuffLds& L, const uint32_t
       break;
     }
     LREFILL();
-    uint32_t e = lit_lookup<false>(L, buf);
+    uint32_t e;
+    if (LEAN) {
+      e = L.lit[(uint32_t)buf & ((1u << kLitRoot) - 1)];
+      if (is_long(e)) {
+        e = L.litsub[(e & 0xffffu) + ((uint32_t)(buf >> kLitRoot) & ((1u << ((e >> 16) & 15u)) - 1))];
+      } else if ((e >> 26) == K_SLOW) {
+        ev = EV_HAND;
+        break;
+      }
+    } else {
+      e = lit_lookup<false>(L, buf);
+    }
     uint32_t n1 = (e >> 16) & 31;
     uint32_t t, len;
     if (e < kKindLit) {
       if (pos + n1 > E) {  // a pair may straddle the end: decode the first literal alone
         if ((e >> 24) == 2u) {
+          if (LEAN) { ev = EV_HAND; break; }
           e = canon_decode<false>(buf, L.cnt_lit, L.sort_lit, 0);
           n1 = (e >> 16) & 31;
         }
@@ -1034,7 +1063,18 @@ __device__ __forceinline__ uint32_t lane_decode(const HuffLds& L, const uint32_t
         len = (e & 511) + ((uint32_t)(buf >> n1) & ((1u << ex) - 1));
         LCONSUME(n1 + ex);
         LREFILL();
-        const uint32_t d = dist_lookup<false>(L, buf);
+        uint32_t d;
+        if (LEAN) {
+          d = L.dist[(uint32_t)buf & ((1u << kDistRoot) - 1)];
+          if (is_long(d)) {
+            d = L.distsub[(d & 0xffffu) + ((uint32_t)(buf >> kDistRoot) & ((1u << ((d >> 16) & 15u)) - 1))];
+          } else if ((d >> 26) == K_SLOW) {
+            ev = EV_HAND;
+            break;
+          }
+        } else {
+          d = dist_lookup<false>(L, buf);
+        }
         const uint32_t dn = (d >> 16) & 31;
         if (d >= kKindLit) {  // invalid distance code
           ev = (pos + max(dn, 1u) > E) ? EV_INPUT : EV_ERR;
@@ -1619,23 +1659,21 @@ constexpr uint32_t kHuffStaticBytes = kHuffLdsBytes + kHuffCtlBytes;
 constexpr uint32_t kHuffStageCap = kHuffStageMaxLds - kHuffStaticBytes;
 static_assert(kHuffStageCap % 16 == 0 && kHuffStageCap >= 16 * 1024, "phase-A LDS budget");
 
-#ifndef HBAM_HUFF_WAVES_PER_SIMD
-#define HBAM_HUFF_WAVES_PER_SIMD 4
-#endif
-constexpr int kHuffWavesPerSimd = HBAM_HUFF_WAVES_PER_SIMD;  // VGPR cap 128 (no spills); LDS admits 4 staged workgroups per CU
-// One decode round of one BGZF block (the body of k_inflate_huff), reading the
-// compressed bits from an LDS copy of the block (STAGE) or from HBM/L2.
+constexpr int kHuffWavesPerSimd = 4;  // VGPR cap 128; LDS admits 4 staged workgroups per CU
+// One decode round of block bx of the chunk (the body of k_huff_fallback),
+// reading the compressed bits from an LDS copy of the block (STAGE) or from
+// HBM/L2.
 template <bool STAGE>
 __device__ __forceinline__ void huff_block(uint8_t* smem, const uint8_t* __restrict__ file,
                                            const BlockInfo* __restrict__ blocks, uint32_t b0, uint64_t chunk_ustart,
                                            uint32_t* __restrict__ tokens, HuffOut* __restrict__ hout,
                                            const uint8_t* __restrict__ tables, const HuffTableInfo* __restrict__ tinfo,
-                                           uint32_t round, uint32_t defer) {
+                                           uint32_t round, uint32_t defer, uint32_t bx) {
   HuffLds& L = *reinterpret_cast<HuffLds*>(smem + kHuffStageCap);
   HuffCtl& C = *reinterpret_cast<HuffCtl*>(smem + kHuffStageCap + kHuffLdsBytes);
   uint4* s_in = reinterpret_cast<uint4*>(smem);
   const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-  const uint32_t bi = b0 + blockIdx.x;
+  const uint32_t bi = b0 + bx;
   const BlockInfo blk = blocks[bi];
   const uint32_t isize = blk.isize;
   if (isize == 0) {  // inflate(buf,off,0) returns 0 without reading: nothing to validate
@@ -1650,7 +1688,7 @@ __device__ __forceinline__ void huff_block(uint8_t* smem, const uint8_t* __restr
   uint32_t* tok_out = tokens + (blk.ustart - chunk_ustart);
   const uint64_t sbyte = blk.coff + 18;  // cdata start
   const uint64_t abase = sbyte & ~15ull;
-  const HuffTableInfo ti = tinfo[blockIdx.x];
+  const HuffTableInfo ti = tinfo[bx];
   {  // stage the block (+16 B of zero-padded file) and its prebuilt tables in LDS
     // One index space over both copies ([0, nq): block, [nq, nq + nt): table
     // image), kStageBatch 16 B loads in flight per thread before their LDS
@@ -1663,7 +1701,7 @@ __device__ __forceinline__ void huff_block(uint8_t* smem, const uint8_t* __restr
     const uint32_t nq = nq_all - q0;
     const uint32_t nt = ti.status == 0 ? kTableImage / 16 : 0u;
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(file + abase) + q0;
-    const uint4* __restrict__ tsrc = reinterpret_cast<const uint4*>(tables + (uint64_t)blockIdx.x * kTableImage);
+    const uint4* __restrict__ tsrc = reinterpret_cast<const uint4*>(tables + (uint64_t)bx * kTableImage);
     uint4* sdst = s_in + q0;
     uint4* tdst = reinterpret_cast<uint4*>(&L);
     // global -> LDS without registers (global_load_lds_dwordx4): each wave
@@ -1965,23 +2003,231 @@ __device__ __forceinline__ void huff_block(uint8_t* smem, const uint8_t* __restr
   }
 }
 
-// Phase A: one 256-thread workgroup per BGZF block of the chunk.  Each
-// workgroup stages its compressed block in LDS when it fits kHuffStageCap,
-// else it reads the bits from HBM/L2: one launch per round whatever the block
-// sizes (a launch used to run unstaged as a whole when one block of the chunk
-// was too big).
-__global__ __launch_bounds__(kHuffThreads, kHuffWavesPerSimd) void k_inflate_huff(
+// Phase A fallback: the blocks of the chunk that the round's lean launch
+// handed over (flist: [round] = their count, [kHuffListHdr ..) = their indices
+// in the chunk), a fixed grid striding over the list.  Each block's round is
+// redone from hout as it was at round entry, so the same token range is
+// rewritten.  A workgroup stages its compressed block in LDS when it fits
+// kHuffStageCap, else it reads the bits from HBM/L2.
+__global__ __launch_bounds__(kHuffThreads, kHuffWavesPerSimd) void k_huff_fallback(
     const uint8_t* __restrict__ file, const BlockInfo* __restrict__ blocks, uint32_t b0, uint64_t chunk_ustart,
     uint32_t* __restrict__ tokens, HuffOut* __restrict__ hout, const uint8_t* __restrict__ tables,
-    const HuffTableInfo* __restrict__ tinfo, uint32_t round, uint32_t defer) {
+    const HuffTableInfo* __restrict__ tinfo, uint32_t round, uint32_t defer, const uint32_t* flist, uint32_t nb,
+    uint32_t* pstats) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[kHuffStageCap + kHuffStaticBytes];
-  const BlockInfo& b = blocks[b0 + blockIdx.x];
-  const uint64_t abase = (b.coff + 18) & ~15ull;
-  const uint32_t need = (uint32_t)(((b.coff + b.csize - abase + 15) >> 4) + 1) * 16u;  // huff_stage_bytes
-  if (need <= kHuffStageCap)
-    huff_block<true>(smem, file, blocks, b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer);
-  else
-    huff_block<false>(smem, file, blocks, b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer);
+  const uint32_t n = min(flist[round], nb);
+  for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const uint32_t bx = flist[kHuffListHdr + i];
+    if (bx >= nb) continue;
+    const BlockInfo& b = blocks[b0 + bx];
+    const uint64_t abase = (b.coff + 18) & ~15ull;
+    const uint32_t need = (uint32_t)(((b.coff + b.csize - abase + 15) >> 4) + 1) * 16u;  // huff_stage_bytes
+    if (need <= kHuffStageCap)
+      huff_block<true>(smem, file, blocks, b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, bx);
+    else
+      huff_block<false>(smem, file, blocks, b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, bx);
+    __syncthreads();  // the next block's staging overwrites this one's LDS
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && n) atomicAdd(&pstats[kPathStatFallback], n);
+}
+
+// ---- the lean instance
+// LDS of a lean workgroup (static, kLeanLds): the staged window at offset 0,
+// the four decode tables (the leading kLeanTableBytes of the table image),
+// the control block.
+#ifndef HBAM_HUFF_WAVES_PER_SIMD
+#define HBAM_HUFF_WAVES_PER_SIMD 5
+#endif
+constexpr int kLeanWavesPerSimd = HBAM_HUFF_WAVES_PER_SIMD;  // 5: VGPR cap 96, 5 workgroups of <= 32 KB per CU
+constexpr uint32_t kLeanTableBytes = offsetof(HuffLds, cnt_lit);  // lit, litsub, dist, distsub
+constexpr uint32_t kLeanStageCap = kLeanLds - kLeanTableBytes - kHuffCtlBytes;
+static_assert(kLeanTableBytes % 16 == 0 && kLeanTableBytes <= kTableImage, "lean tables: a prefix of the table image");
+static_assert(kLeanLds <= 64 * 1024 && kLeanStageCap % 16 == 0 && kLeanStageCap >= 8 * 1024, "lean LDS budget");
+// bits a walk may read past its region end: a lane's exit lies up to one
+// symbol (48 bits) past its stop, and the slow path's reader holds four
+// words from the word of that position on
+constexpr uint32_t kLeanReadPast = 48 + 128;
+
+// One round of block blockIdx.x decoded from its prebuilt tables: the passes
+// of huff_block over one DEFLATE block (stage, speculate, sync, emit, and the
+// same-tables continuation), every lane taking the (uniform) decisions wave 0
+// takes there.  Handled inline: the end-of-block that leaves the block
+// pending (defer), output overfull (EV_FULLO), and output exactly full
+// (EV_FULLX) where the next code is an end-of-block inside CDATA of a final
+// block -- the end of every well-formed BGZF block.  Returns false, with hout
+// untouched, for everything else: the fallback redoes the round.
+// Bit positions are relative to the 16 B unit the staged window starts at.
+__device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restrict__ file, const BlockInfo& blk,
+                                           uint32_t* __restrict__ tok_out, HuffOut& h, const uint8_t* __restrict__ timg,
+                                           const HuffTableInfo& ti, uint32_t isize, uint32_t defer) {
+  if (ti.status != 0) return false;  // no prebuilt tables: stored / fixed block, an anomalous header
+  HuffLds& L = *reinterpret_cast<HuffLds*>(smem + kLeanStageCap);  // (only its leading kLeanTableBytes exist)
+  HuffCtl& C = *reinterpret_cast<HuffCtl*>(smem + kLeanStageCap + kLeanTableBytes);
+  const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+  const uint64_t sbyte = blk.coff + 18;  // cdata start
+  const uint64_t abase = sbyte & ~15ull;
+  const uint32_t Eabs = 8u * ((uint32_t)(sbyte - abase) + (blk.csize - 26));  // end of CDATA
+  if (ti.B0 > Eabs) return false;
+  const bool final_blk = ti.final_blk != 0;
+  const uint32_t est = ti.est_bits;
+  const uint32_t bend_abs = pass_end(ti.B0, est, final_blk, Eabs);
+  // the round's window, in 16 B units of the block (+16 B of zero-padded file)
+  const uint32_t nq_all = (uint32_t)((blk.coff + blk.csize - abase + 15) >> 4) + 1;
+  const uint32_t q0 = min(ti.B0 >> 7, nq_all);
+  const uint32_t q1 = min(((bend_abs + kLeanReadPast) >> 7) + 1, nq_all);
+  const uint32_t nq = q1 > q0 ? q1 - q0 : 0u;
+  if (nq * 16u > kLeanStageCap) return false;  // a window larger than the stage
+  {  // stage the window and the tables (global -> LDS without registers, as huff_block)
+    const uint4* __restrict__ src = reinterpret_cast<const uint4*>(file + abase) + q0;
+    const uint4* __restrict__ tsrc = reinterpret_cast<const uint4*>(timg);
+    uint4* sdst = reinterpret_cast<uint4*>(smem);
+    uint4* tdst = reinterpret_cast<uint4*>(&L);
+    constexpr uint32_t nt = kLeanTableBytes / 16;
+    typedef __attribute__((address_space(3))) void* lds_vp;
+    typedef __attribute__((address_space(1))) void* gbl_vp;
+    for (uint32_t u0 = 64 * wave; u0 < nq; u0 += kHuffThreads)
+      if (u0 + lane < nq) __builtin_amdgcn_global_load_lds((gbl_vp)(src + u0 + lane), (lds_vp)(sdst + u0), 16, 0, 0);
+    for (uint32_t u0 = 64 * wave; u0 < nt; u0 += kHuffThreads)
+      if (u0 + lane < nt) __builtin_amdgcn_global_load_lds((gbl_vp)(tsrc + u0 + lane), (lds_vp)(tdst + u0), 16, 0, 0);
+  }
+  __syncthreads();
+  const uint32_t* __restrict__ W = reinterpret_cast<const uint32_t*>(smem);
+  const uint32_t bias = q0 << 7;
+  const uint32_t E = Eabs - bias;
+  // bits a later pass may read: everything staged, or (the block's end is
+  // staged) whatever huff_block reads
+  const uint32_t read_end = q1 == nq_all ? 0xffffffffu : nq << 7;
+  uint32_t B0 = ti.B0 - bias, Bend = bend_abs - bias;
+  uint32_t outpos = h.outpos, ntok = h.ntok;
+  for (;;) {
+    // ---- all-lane decode of [B0, Bend)
+    const uint32_t R = Bend > B0 ? Bend - B0 : 0u;
+    const uint32_t S = (R + kHuffThreads - 1) / kHuffThreads;
+    uint32_t a = min(B0 + tid * S, Bend);
+    const uint32_t stop = tid == kHuffThreads - 1 ? Bend : min(B0 + (tid + 1) * S, Bend);
+    MergePts mp;
+    uint32_t mj = 0, x, nt, nb;
+    const uint32_t mf = S < kMergeTinyBits ? kMergeFirst / 4 : S < kMergeShortBits ? kMergeFirst / 2 : kMergeFirst;
+    uint32_t ev = lane_decode<LD_SPEC, true>(L, W, a, stop, E, x, nt, nb, mp, mj, nullptr, 0, 0, mf);
+    const uint32_t sx = x, snt = nt, snb = nb, sev = ev;
+    for (;;) {  // sync: restart each slice from its predecessor's exit
+      if (lane == 63) {
+        C.xx[wave] = x;
+        C.xe[wave] = ev;
+      }
+      __syncthreads();
+      uint32_t px = __shfl_up(x, 1, 64), pev = __shfl_up(ev, 1, 64);
+      if (lane == 0 && wave > 0) {
+        px = C.xx[wave - 1];
+        pev = C.xe[wave - 1];
+      }
+      const bool need = tid > 0 && pev == EV_STOP && px != a;
+      if (!wg_any(need, C.red)) break;
+      if (need) {
+        a = px;
+        uint32_t rx, rnt, rnb;
+        const uint32_t rev = lane_decode<LD_SYNC, true>(L, W, a, stop, E, rx, rnt, rnb, mp, mj, nullptr, 0, 0, mf);
+        if (rev == EV_MERGE) {  // shares the speculative walk from boundary mj on
+          const uint32_t bj = mj == 0 ? mp.b0 : mj == 1 ? mp.b1 : mj == 2 ? mp.b2 : mp.b3;
+          x = sx;
+          ev = sev;
+          nt = rnt + snt - (mf << mj);
+          nb = rnb + snb - bj;
+        } else {
+          x = rx;
+          ev = rev;
+          nt = rnt;
+          nb = rnb;
+        }
+      }
+    }
+    const uint32_t lend0 = wg_min(ev != EV_STOP ? tid : 0xffffffffu, C.red);
+    const uint32_t lend = lend0 == 0xffffffffu ? (uint32_t)kHuffThreads - 1 : lend0;
+    const bool valid = tid <= lend;
+    uint32_t toff, boff;
+    wg_excl_scan2(valid ? nt : 0u, valid ? nb : 0u, C.red, toff, boff);
+    uint32_t x3 = a, nt3 = 0, nb3 = 0, ev3 = EV_STOP;
+    if (valid)
+      ev3 = lane_decode<LD_EMIT, true>(L, W, a, stop, E, x3, nt3, nb3, mp, mj, tok_out + ntok + toff, outpos + boff,
+                                       isize);
+    const uint32_t m3 = wg_min((valid && ev3 != EV_STOP) ? tid : 0xffffffffu, C.red);
+    const uint32_t f = m3 != 0xffffffffu ? m3 : lend;
+    if (tid == f) {
+      C.fe = ev3;
+      C.fx = x3;
+      C.ftok = toff + nt3;
+      C.fbytes = boff + nb3;
+      C.m3any = m3 != 0xffffffffu;
+    }
+    __syncthreads();
+    // ---- the pass's result (uniform)
+    const uint32_t fe = rfl(C.fe), fxs = rfl(C.fx), m3any = rfl(C.m3any);
+    ntok = rfl(ntok + C.ftok);
+    outpos = rfl(outpos + C.fbytes);
+    if (!m3any) {
+      // the pass ended at its region end inside the block: go on with the
+      // same tables over the next stretch, if it is staged
+      if (!(Bend < E && fxs < E && outpos < isize)) return false;
+      const uint32_t bnext = min(E, fxs + (est >> 2) + 4096u);
+      if (bnext + kLeanReadPast > read_end) return false;
+      B0 = fxs;
+      Bend = bnext;
+      continue;
+    }
+    if (fe == EV_EOB) {
+      if (final_blk || !defer) return false;  // an early end (error), or a header for this round
+      h = HuffOut{ntok, kHuffPending, fxs + bias, outpos};  // the next header is the next round's
+      return true;
+    }
+    if (fe == EV_FULLX) {  // zlib's lookahead: the final block's end-of-block, inside CDATA
+      const uint32_t wd = fxs >> 5;
+      const uint32_t lo = __builtin_amdgcn_alignbit(W[wd + 1], W[wd], fxs & 31);
+      uint32_t e = L.lit[lo & ((1u << kLitRoot) - 1)];
+      if (is_long(e))
+        e = L.litsub[min((e & 0xffffu) + __builtin_amdgcn_ubfe(lo, kLitRoot, (e >> 16) & 15u),
+                         (uint32_t)kLitSubCap - 1)];
+      e = rfl(e);
+      if (!final_blk || (e >> 26) != K_EOB || fxs + ((e >> 16) & 31) > E) return false;
+    } else if (fe != EV_FULLO) {
+      return false;  // an error event, input exhausted, a canonical-decode entry
+    }
+    h = HuffOut{ntok, kOk, 0u, outpos};
+    return true;
+  }
+}
+
+// Phase A, lean instance: one 256-thread workgroup per BGZF block of the
+// chunk, one DEFLATE block per round.  A block whose round it does not handle
+// is appended to flist for k_huff_fallback (launched behind it).  pstats
+// counts the rounds it completed, spread over kPathStatSlots words.
+__global__ __launch_bounds__(kHuffThreads, kLeanWavesPerSimd) void k_inflate_huff(
+    const uint8_t* __restrict__ file, const BlockInfo* __restrict__ blocks, uint32_t b0, uint64_t chunk_ustart,
+    uint32_t* __restrict__ tokens, HuffOut* __restrict__ hout, const uint8_t* __restrict__ tables,
+    const HuffTableInfo* __restrict__ tinfo, uint32_t round, uint32_t defer, uint32_t* flist, uint32_t* pstats) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[kLeanLds];
+  const uint32_t bi = b0 + blockIdx.x;
+  const BlockInfo blk = blocks[bi];
+  const uint32_t isize = blk.isize;
+  if (isize == 0) {  // inflate(buf,off,0) returns 0 without reading: nothing to validate
+    if (threadIdx.x == 0 && round == 0) { hout[bi].ntok = 0; hout[bi].status = kOk; }
+    return;
+  }
+  HuffOut h{0u, kOk, 0u, 0u};
+  if (round > 0) {  // only blocks a previous round left pending
+    h = hout[bi];
+    if (h.status != kHuffPending) return;
+  }
+  const HuffTableInfo ti = tinfo[blockIdx.x];
+  const bool done = lean_block(smem, file, blk, tokens + (blk.ustart - chunk_ustart), h,
+                               tables + (uint64_t)blockIdx.x * kTableImage, ti, isize, defer);
+  if (threadIdx.x == 0) {
+    if (done) {
+      hout[bi] = h;
+      atomicAdd(&pstats[kPathStatLean + (blockIdx.x % kPathStatSlots) * kPathStatStride], 1u);
+    } else {
+      flist[kHuffListHdr + atomicAdd(&flist[round], 1u)] = blockIdx.x;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -4098,12 +4344,17 @@ hipError_t launch_huff_tables(const uint8_t* file, const BlockInfo* blocks, uint
 hipError_t launch_inflate_huff_prebuilt(const uint8_t* file, const BlockInfo* blocks, uint32_t b0, uint32_t nb,
                                         uint64_t chunk_ustart, uint32_t* tokens, HuffOut* hout,
                                         const uint8_t* tables, const HuffTableInfo* tinfo, uint32_t round,
-                                        uint32_t defer, hipStream_t s) {
-  // (every workgroup decides for its own block whether it stages it, k_inflate_huff)
+                                        uint32_t defer, uint32_t* flist, uint32_t* pstats, hipStream_t s) {
   if (nb == 0) return hipSuccess;
+  // the lean instance over the chunk, then the fallback over the blocks it handed over
   hipLaunchKernelGGL(k_inflate_huff, dim3(nb), dim3(kHuffThreads), 0, s, file, blocks, b0, chunk_ustart, tokens,
-                     hout, tables, tinfo, round, defer);
+                     hout, tables, tinfo, round, defer, flist, pstats);
+  hipLaunchKernelGGL(k_huff_fallback, dim3(std::min(nb, kHuffFallbackGrid)), dim3(kHuffThreads), 0, s, file, blocks,
+                     b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, nb, pstats);
   return hipGetLastError();
+}
+hipError_t huff_lean_occupancy(int* workgroups_per_cu) {
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, k_inflate_huff, kHuffThreads, 0);
 }
 hipError_t launch_inflate_lz77(const BlockInfo* blocks, uint32_t b0, uint32_t nb, uint64_t chunk_ustart,
                                const uint32_t* tokens, const HuffOut* hout, uint8_t* u, hipStream_t s) {

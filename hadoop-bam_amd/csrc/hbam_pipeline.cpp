@@ -64,7 +64,7 @@ Pipeline::Pipeline(int device) : device_(device) {
   stage_owner_.n = 2;
   stage_.owner = &stage_owner_;
   own(own_file_, own_spare_, dblocks_, ref_len_, du_, tokens_[0], tokens_[1], hout_, tables_[0], tables_[1],
-      tinfo_[0], tinfo_[1], g_, x_, x2_, entry_, base_arr_, summary_, dead_, cand_, sorted_, isz_, ust_, cnt_, flags_,
+      tinfo_[0], tinfo_[1], flist_[0], flist_[1], pstats_, g_, x_, x2_, entry_, base_arr_, summary_, dead_, cand_, sorted_, isz_, ust_, cnt_, flags_,
       errv_, need_, rec_pos_, rec_voff_, rcand_, force_, wcnt_, counters_, list_, scan_tmp_, cols_, long_rec_,
       long_n_, wbuf_, woffs_, wbad_, scalars_, fuse_);
   for (auto& e : ev_) (void)hipEventCreate(&e);
@@ -338,6 +338,21 @@ int Pipeline::inflate_tokens(uint64_t* n) {
   return kOk;
 }
 
+int Pipeline::inflate_path_counts(uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  HIPCHK(hipSetDevice(device_));
+  int wgs = 0;
+  HIPCHK(huff_lean_occupancy(&wgs));
+  out[2] = (uint64_t)wgs;
+  if (!pstats_.p) return kOk;  // nothing inflated yet
+  std::vector<uint32_t> st(kPathStatWords);
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipMemcpy(st.data(), pstats_.p, kPathStatWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < kPathStatSlots; ++k) out[0] += st[kPathStatLean + k * kPathStatStride];
+  out[1] = st[kPathStatFallback];
+  return kOk;
+}
+
 int Pipeline::set_ref_lengths(const std::vector<int32_t>& lens) {
   HIPCHK(ref_len_.reserve(lens.size() + 1));
   if (!lens.empty())
@@ -528,7 +543,9 @@ int Pipeline::run_streamed(const uint8_t* data, uint64_t len, uint64_t piece, ui
   for (int i = 0; i < 2; ++i) {
     HIPCHK(tables_[i].reserve((uint64_t)kInflateChunkBlocks * kHuffTableImage));
     HIPCHK(tinfo_[i].reserve(kInflateChunkBlocks));
+    HIPCHK(flist_[i].reserve(kHuffListHdr + kInflateChunkBlocks));
   }
+  HIPCHK(pstats_.reserve(kPathStatWords));
   HIPCHK(streams_.sync());
 
   // Piece k's copy and its locate run in order on stream_copy_, the inflate
@@ -656,7 +673,10 @@ int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool joi
       HIPCHK(tokens_[i].reserve(max_u + 16));  // phase B reads tokens as uint4
       HIPCHK(tables_[i].reserve(max_nb * kHuffTableImage));
       HIPCHK(tinfo_[i].reserve(max_nb));
+      HIPCHK(flist_[i].reserve(kHuffListHdr + max_nb));
     }
+    HIPCHK(pstats_.reserve(kPathStatWords));
+    HIPCHK(hipMemsetAsync(pstats_.p, 0, kPathStatWords * sizeof(uint32_t), stream_));
     if (!serial) {  // phase B and the table builds see everything queued on stream_ before this call
       HIPCHK(hipEventRecord(sync_ev_[0], stream_));
       HIPCHK(hipStreamWaitEvent(stream_b_, sync_ev_[0], 0));
@@ -678,6 +698,9 @@ int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool joi
     // (the first chunk's round-0 tables run on stream_ itself: nothing runs
     // beside them, and a cross-stream wait costs ~15 us at the pass's start)
     const bool t_own = !serial && j > 0;
+    // (the list is written and read on stream_ only: the chunk of the same
+    // parity before this one is done with it)
+    HIPCHK(hipMemsetAsync(flist_[par].p, 0, kHuffListHdr * sizeof(uint32_t), stream_));
     for (uint32_t r = 0; r < kInflateRounds; ++r) {
       HIPCHK(mark());
       HIPCHK(launch_huff_tables(fbase, dblocks_.p, cb, ce - cb, tables_[par].p, tinfo_[par].p, hout_.p, r,
@@ -690,7 +713,7 @@ int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool joi
       HIPCHK(mark());
       HIPCHK(launch_inflate_huff_prebuilt(fbase, dblocks_.p, cb, ce - cb, cu, tokens_[par].p, hout_.p,
                                           tables_[par].p, tinfo_[par].p, r, r + 1 < kInflateRounds ? 1u : 0u,
-                                          stream_));
+                                          flist_[par].p, pstats_.p, stream_));
       HIPCHK(mark());
     }
     // the last chunk's phase B on stream_ itself: nothing of this call is

@@ -311,6 +311,11 @@ class Pipeline {
   // LZ77 tokens phase A wrote for the window's blocks in its last inflate
   // (the sum of HuffOut::ntok; a synchronous read, for measurements)
   int inflate_tokens(uint64_t* n);
+  // Phase A's paths in the last inflate (a synchronous read, for
+  // measurements): out[0] = block rounds the lean instance decoded, out[1] =
+  // block rounds it handed to the fallback, out[2] = resident workgroups per
+  // CU the runtime reports for the lean instance
+  int inflate_path_counts(uint64_t out[3]);
   StageTimes times;
   bool timing = false;  // record per-stage HIP event times
 
@@ -394,6 +399,8 @@ class Pipeline {
   hipEvent_t hdone_ev_[2];          // phase A of the chunk of that parity done (tables free)
   hipEvent_t sync_ev_[4];           // [0,1] phase A done, [2,3] phase B done, per token buffer
   DevBuf<HuffTableInfo> tinfo_[2];
+  DevBuf<uint32_t> flist_[2];  // phase A's hand-over lists (per chunk, by chunk parity)
+  DevBuf<uint32_t> pstats_;    // phase A's path counters of the last inflate (kPathStatWords)
 
   // span scratch
   DevBuf<uint64_t> g_, x_, x2_, entry_, base_arr_, summary_, dead_;

@@ -98,6 +98,7 @@ _sig("hbam_query_unmapped", C.c_int, [P, u64])
 _sig("hbam_query_next", C.c_int, [P, u64, C.POINTER(Batch)])
 _sig("hbam_pipeline_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_token_count", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_inflate_path_counts", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_file_stats", C.c_int, [P, C.POINTER(u64), C.POINTER(u64)])
 _sig("hbam_bytes_read", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_prefetch", C.c_int, [P, u64, u64])
@@ -466,6 +467,16 @@ class BamFile:
         if rc != OK:
             raise self._err(rc)
         return int(v.value)
+
+    def inflate_path_counts(self):
+        """(lean, fallback, resident): block decode rounds of the last inflate
+        that phase A's lean kernel decoded / handed to the fallback kernel, and
+        the lean kernel's resident workgroups per CU (hbam_inflate_path_counts)."""
+        v = (u64 * 3)()
+        rc = _L.hbam_inflate_path_counts(self._h, v)
+        if rc != OK:
+            raise self._err(rc)
+        return int(v[0]), int(v[1]), int(v[2])
 
     def decode_span_device(self, vstart, vend, timing=False, decode=True, digest=True):
         """The span decoded with the records left in HBM: stats dict."""

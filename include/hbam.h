@@ -427,6 +427,16 @@ int hbam_pipeline_counters(hbam_ctx *ctx, uint64_t out[5]);
  * counterpart); synchronous. */
 int hbam_inflate_token_count(hbam_ctx *ctx, uint64_t *tokens);
 
+/* Which of inflate phase A's two kernels decoded the ctx's last inflate,
+ * counted per block and decode round (a BGZF block of two DEFLATE blocks
+ * takes two rounds): out[0] block rounds the lean instance decoded, out[1]
+ * block rounds it handed to the fallback kernel, out[2] the resident
+ * workgroups per CU the runtime reports for the lean instance (its answer:
+ * a process that has a second copy of the HIP runtime loaded can be told
+ * less than the hardware runs).  A measurement helper (no reference
+ * counterpart); synchronous, the counters are read only here. */
+int hbam_inflate_path_counts(hbam_ctx *ctx, uint64_t out[3]);
+
 /* The sharded SplittingBAMIndexer.index (SplittingBAMIndexer.java:262-287,
  * SURVEY 8e step 3): the records of FileVirtualSplit [vstart, vend) read
  * under the indexer's rules (readAlignment/fullySkip, :340-368), their count
