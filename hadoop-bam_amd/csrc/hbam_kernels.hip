@@ -344,7 +344,11 @@ constexpr int kDistRoot = 9;
 // long-code prefix holds the sub-table base and its index width (= the longest
 // code under that prefix - root).  A complete litlen code with a 10-bit root
 // needs at most 310 sub entries (zlib ENOUGH_LENS 1334 - 1024), the distance
-// code with a 9-bit root at most 80 (ENOUGH_DISTS 592 - 512); build_table
+// code with a 9-bit root at most 80: the largest sum of 2^(longest code under
+// a prefix - root) over every complete code of up to 30 symbols and 15 bits,
+// by enumeration of their length distributions (zlib's ENOUGH_DISTS 592 is
+// the figure for its 6-bit root and says nothing here); case T2 of
+// tests/deflate_cases.py reaches 306 and 80.  build_table
 // accepts complete codes only (and the one-code case).  Prefixes that would
 // not fit fall back to K_SLOW (canonical decode), which valid streams never
 // reach.  The caps size the table image every block writes and phase A reads

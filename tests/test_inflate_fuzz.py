@@ -12,9 +12,11 @@ import struct
 import numpy as np
 import pytest
 
+import deflate_enc
 import hbam
 import orc
 from hbam import synth
+from test_gpu_inflate_lean import EOF_BLOCK, bgzf
 
 pytestmark = pytest.mark.gpu
 
@@ -104,43 +106,15 @@ def _fixed_block_with_distance_code(dcode, nlit=400):
     length-3 match with distance code dcode (30 and 31 are invalid in
     DEFLATE), nlit more literals and the end-of-block code.  The match lies
     thousands of bits before the end, in the decoder's fast region."""
-    import zlib
-    bits, nbits = 0, 0
-
-    def put(v, n):  # n bits, LSB first
-        nonlocal bits, nbits
-        bits |= v << nbits
-        nbits += n
-
-    def put_code(c, n):  # a Huffman code, MSB first
-        put(int(format(c, "0%db" % n)[::-1], 2), n)
-
-    def lit(v):
-        if v < 144:
-            put_code(0x30 + v, 8)
-        else:
-            put_code(0x190 + v - 144, 9)
-
     rng = np.random.default_rng(dcode)
     body = bytes(rng.integers(65, 91, nlit, dtype=np.uint8))
-    put(1, 1)  # BFINAL
-    put(1, 2)  # fixed Huffman
-    for b in body:
-        lit(b)
-    put_code(1, 7)  # length code 257: length 3
-    put_code(dcode, 5)  # distance code, 5 bits (no extra bits for 0-3; 30/31 invalid)
-    if dcode >= 4:
-        put(0, (dcode - 2) // 2)
-    for b in body:
-        lit(b)
-    put_code(0, 7)  # end of block
-    cdata = bits.to_bytes((nbits + 7) // 8, "little")
+    lits = [("L", b) for b in body]
+    w = deflate_enc.BitWriter()
+    # length code 257 (length 3), then the distance code raw, its extra bits zero
+    match = ("R", 257, (0, 0), dcode, (0, (dcode - 2) // 2 if dcode >= 4 else 0))
+    deflate_enc.put_fixed(w, lits + [match] + lits, True)
     out = body + (body[-4:-1] if dcode == 3 else b"...") + body  # (only the length matters for ISIZE)
-    isize = len(out)
-    hdr = bytes([31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0]) + struct.pack("<H", len(cdata) + 25)
-    blk = hdr + cdata + struct.pack("<II", zlib.crc32(out) & 0xffffffff, isize)
-    eof = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-    return blk + eof
+    return bgzf(w.getvalue(), out) + EOF_BLOCK
 
 
 @pytest.mark.parametrize("dcode", [30, 31])
