@@ -494,6 +494,12 @@ int hbam_inflate_path_counts(hbam_ctx* ctx, uint64_t out[3]) {
   return ctx->f->pipe().inflate_path_counts(out) == 0 ? HBAM_OK : HBAM_E_DEVICE;
 }
 
+int hbam_chain_counters(hbam_ctx* ctx, uint64_t out[4]) {
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  return ctx->f->pipe().chain_counters(out) == 0 ? HBAM_OK : HBAM_E_DEVICE;
+}
+
 int hbam_decode_span_device(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_t flags, hbam_gpu_stats* st) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   reset_cursors(ctx);

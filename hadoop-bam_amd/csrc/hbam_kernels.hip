@@ -3670,10 +3670,11 @@ template <int MODE>
 __global__ __launch_bounds__(64) void k_rec_search(ChainEnv E, const uint64_t* __restrict__ cand,
                                                    uint64_t* __restrict__ g_out, uint64_t* __restrict__ x_out,
                                                    uint32_t* __restrict__ wcnt, uint16_t* __restrict__ list,
-                                                   uint32_t* __restrict__ overflow) {
+                                                   uint32_t* __restrict__ overflow, uint32_t* __restrict__ searched) {
   const uint32_t i = blockIdx.x;
   if (g_out[i] != kRetry) return;
   const uint32_t lane = lane_id();
+  if (lane == 0) atomicAdd(searched, 1u);  // (hbam_chain_counters)
   const BlockInfo b = E.blocks[E.k0 + i];
   const uint64_t bend = b.ustart + b.isize;
   {  // the walks below are dependent-load chains: pull the block (+ the
@@ -3756,6 +3757,7 @@ __global__ void k_rec_linkfix(ChainEnv E, const uint64_t* __restrict__ g, const 
     if (gi != kNone && x[i] > in) {  // a stray walk would corrupt later in[]
       force[i] = kForceEmpty;
       atomicAdd(&counters[1], 1u);
+      atomicAdd(&counters[kChainCtrDropped], 1u);
     }
   } else if (in < b.ustart) {
     atomicAdd(&counters[0], 1u);  // a block before stopped inside itself
@@ -3764,6 +3766,7 @@ __global__ void k_rec_linkfix(ChainEnv E, const uint64_t* __restrict__ g, const 
     if (gi != in) {
       force[i] = in;
       atomicAdd(&counters[1], 1u);
+      atomicAdd(&counters[kChainCtrRewalked], 1u);
     }
   }
   entry[i] = e;
@@ -4404,13 +4407,13 @@ hipError_t launch_chain(const ChainArgs& a, int mode, int stage, hipStream_t s) 
         hipLaunchKernelGGL(k_rec_walk<kReader>, dim3((nb + 255) / 256), dim3(256), 0, s, E, a.cand, nullptr, a.g,
                            a.x, a.wcnt, a.list, a.counters + 2, false);
         hipLaunchKernelGGL(k_rec_search<kReader>, dim3(nb), dim3(64), 0, s, E, a.cand, a.g, a.x, a.wcnt, a.list,
-                           a.counters + 2);
+                           a.counters + 2, a.counters + kChainCtrSearched);
       } else {
         hipLaunchKernelGGL(k_rec_cand<kIndexer>, dim3(nb), dim3(64), 0, s, E, a.cand);
         hipLaunchKernelGGL(k_rec_walk<kIndexer>, dim3((nb + 255) / 256), dim3(256), 0, s, E, a.cand, nullptr, a.g,
                            a.x, a.wcnt, a.list, a.counters + 2, false);
         hipLaunchKernelGGL(k_rec_search<kIndexer>, dim3(nb), dim3(64), 0, s, E, a.cand, a.g, a.x, a.wcnt, a.list,
-                           a.counters + 2);
+                           a.counters + 2, a.counters + kChainCtrSearched);
       }
       break;
     }

@@ -32,13 +32,21 @@ struct ChainArgs {
   uint64_t* force;      // re-walk requests (kNone = keep)
   uint32_t* wcnt;       // records listed per block
   uint16_t* list;       // kListCap u16 offsets (from ustart) per block
-  uint32_t* counters;   // [0] hard link violations, [1] blocks to re-walk, [2] list overflow
+  uint32_t* counters;   // [0] hard link violations, [1] blocks to re-walk, [2] list overflow (zeroed per pass);
+                        // [kChainCtr..]: cumulative path counters (zeroed once, hbam_chain_counters)
   // fused check + output (launch_rec_check_out)
   uint64_t* fuse_bad;    // = ~0: min (i << kFusedBadShift | records up to i's stop) over blocks that stop early
   uint32_t* fuse_flags;  // [0] first failing block = ~0
 };
 constexpr uint32_t kListCap = 2048;              // >= 65536 / 36 + 2: every reader-mode record start
 constexpr uint64_t kForceEmpty = ~0ull - 1;      // force[]: the block holds no record start
+// ChainArgs::counters words past the per-pass ones: written only on the rare
+// paths they count, never zeroed after the buffer's allocation
+constexpr uint32_t kChainCtr = 4;          // first cumulative word
+constexpr uint32_t kChainCtrSearched = 4;  // blocks handed to k_rec_search (first candidate's walk failed)
+constexpr uint32_t kChainCtrRewalked = 5;  // blocks the link check re-walks from a forced entry
+constexpr uint32_t kChainCtrDropped = 6;   // stray walks the link check drops (kForceEmpty)
+constexpr uint32_t kChainCtrWords = 8;     // the buffer's size in words
 
 // launch_chain stages
 enum ChainStage : int {

@@ -353,6 +353,20 @@ int Pipeline::inflate_path_counts(uint64_t out[3]) {
   return kOk;
 }
 
+int Pipeline::chain_counters(uint64_t out[4]) {
+  out[0] = out[1] = out[2] = 0;
+  out[3] = link_rounds_;
+  if (!counters_.p) return kOk;  // no record pass yet
+  HIPCHK(hipSetDevice(device_));
+  uint32_t w[3] = {0, 0, 0};
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipMemcpy(w, counters_.p + kChainCtr, sizeof(w), hipMemcpyDeviceToHost));
+  out[0] = w[kChainCtrSearched - kChainCtr];
+  out[1] = w[kChainCtrRewalked - kChainCtr];
+  out[2] = w[kChainCtrDropped - kChainCtr];
+  return kOk;
+}
+
 int Pipeline::set_ref_lengths(const std::vector<int32_t>& lens) {
   HIPCHK(ref_len_.reserve(lens.size() + 1));
   if (!lens.empty())
@@ -931,7 +945,10 @@ int Pipeline::decode_span_pos(uint64_t p0, uint64_t vend, ChainMode mode, bool d
     HIPCHK(wcnt_.reserve(nb));
     HIPCHK(list_.reserve((uint64_t)nb * kListCap));
     HIPCHK(base_arr_.reserve(nb + 1));
-    HIPCHK(counters_.reserve(4));
+    if (!counters_.p) {  // the cumulative words (kChainCtr..) are zeroed here only
+      HIPCHK(counters_.reserve(kChainCtrWords));
+      HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtrWords * 4, stream_));
+    }
     size_t lsb = 0;
     HIPCHK(link_scan_bytes(nb, &lsb));
     HIPCHK(scan_tmp_.reserve(lsb + 16));
@@ -952,7 +969,7 @@ int Pipeline::decode_span_pos(uint64_t p0, uint64_t vend, ChainMode mode, bool d
     a.scan_tmp = scan_tmp_.p;
     a.scan_bytes = lsb;
     HIPCHK(hipMemsetAsync(need_.p, 0, 8, stream_));
-    HIPCHK(hipMemsetAsync(counters_.p, 0, 16, stream_));
+    HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtr * 4, stream_));  // the per-pass words only
     HIPCHK(launch_chain(a, mode, kStageWalk, stream_));  // candidates + lane-per-block walks
     // link: max-scan of the walk exits; re-walk blocks that are off the chain
     bool serial = false;
@@ -1009,6 +1026,7 @@ int Pipeline::decode_span_pos(uint64_t p0, uint64_t vend, ChainMode mode, bool d
     for (int fix = 0;; ++fix) {
       HIPCHK(hipMemsetAsync(counters_.p, 0, 8, stream_));
       HIPCHK(launch_chain(a, mode, kStageLinkCheck, stream_));
+      ++link_rounds_;
       uint32_t ctr[2] = {0, 0};
       HIPCHK(rb(ctr, counters_.p, 8, stream_));
       // first round: queue the chain end and the list bound as if the link

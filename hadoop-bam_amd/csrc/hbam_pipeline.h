@@ -316,6 +316,11 @@ class Pipeline {
   // block rounds it handed to the fallback, out[2] = resident workgroups per
   // CU the runtime reports for the lean instance
   int inflate_path_counts(uint64_t out[3]);
+  // The record chain's rare paths since the open (a synchronous read, for
+  // tests): out[0] = blocks handed to k_rec_search, out[1] = blocks the link
+  // check re-walked from a forced entry, out[2] = stray walks it dropped,
+  // out[3] = link-check rounds
+  int chain_counters(uint64_t out[4]);
   StageTimes times;
   bool timing = false;  // record per-stage HIP event times
 
@@ -382,6 +387,7 @@ class Pipeline {
   uint32_t n_ref_len_ = 0;
   uint64_t link_fallbacks_ = 0;
   uint64_t link_rewalks_ = 0;      // re-walk rounds of the parallel link
+  uint64_t link_rounds_ = 0;       // link-check launches (one per pass when every guess is on the chain)
   uint64_t record_fallbacks_ = 0;  // spans whose lists overflowed: records counted and emitted by walks
   uint64_t records_after_stop_ = 0;  // spans that stopped early with records listed in later blocks (dropped)
   uint32_t after_stop_flag_ = 0;     // (read back with a span's last readback)

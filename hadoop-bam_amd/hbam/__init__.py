@@ -99,6 +99,7 @@ _sig("hbam_query_next", C.c_int, [P, u64, C.POINTER(Batch)])
 _sig("hbam_pipeline_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_token_count", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_path_counts", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_chain_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_file_stats", C.c_int, [P, C.POINTER(u64), C.POINTER(u64)])
 _sig("hbam_bytes_read", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_prefetch", C.c_int, [P, u64, u64])
@@ -477,6 +478,17 @@ class BamFile:
         if rc != OK:
             raise self._err(rc)
         return int(v[0]), int(v[1]), int(v[2])
+
+    def chain_counters(self):
+        """Cumulative counters of the record chain's rare paths
+        (hbam_chain_counters): blocks searched past their first candidate,
+        blocks re-walked from a forced entry, stray walks dropped, link-check
+        rounds."""
+        v = (u64 * 4)()
+        rc = _L.hbam_chain_counters(self._h, v)
+        if rc != OK:
+            raise self._err(rc)
+        return dict(zip(("searched", "rewalked", "dropped", "link_rounds"), (int(x) for x in v)))
 
     def decode_span_device(self, vstart, vend, timing=False, decode=True, digest=True):
         """The span decoded with the records left in HBM: stats dict."""

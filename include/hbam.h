@@ -437,6 +437,20 @@ int hbam_inflate_token_count(hbam_ctx *ctx, uint64_t *tokens);
  * counterpart); synchronous, the counters are read only here. */
 int hbam_inflate_path_counts(hbam_ctx *ctx, uint64_t out[3]);
 
+/* Which rare paths the ctx's record chain took, cumulative since the open
+ * over every call (hbam_pipeline_counters counts spans and rounds; these
+ * count blocks): out[0] BGZF blocks whose first plausible record start gave a
+ * walk that failed, so that later starts were searched, out[1] blocks whose
+ * walk was off the true chain and that the link check asked to re-walk from
+ * the chain's entry (counted per round, also when the walk refuses the entry
+ * because the chain from it is not plausible), out[2] walks in blocks lying wholly inside one record that
+ * the link check dropped because their exit would have misled later blocks,
+ * out[3] link-check rounds (one per record pass when every walk is on the
+ * chain).  out[0..2] are 32-bit on the device and wrap.  Diagnostics (no
+ * reference counterpart): tests assert which path a decode took;
+ * synchronous, the device counters are read only here. */
+int hbam_chain_counters(hbam_ctx *ctx, uint64_t out[4]);
+
 /* The sharded SplittingBAMIndexer.index (SplittingBAMIndexer.java:262-287,
  * SURVEY 8e step 3): the records of FileVirtualSplit [vstart, vend) read
  * under the indexer's rules (readAlignment/fullySkip, :340-368), their count
