@@ -476,9 +476,19 @@ int for_each_window(BamFile& f, std::vector<GuessPoint>& pts, F&& body) {
   return hbam::kOk;
 }
 
-// Load + locate + inflate + CRC-check the window; *valid[k] per block.
-int prepare_window(BamFile& f, uint64_t lo, uint64_t hi, hbam::DevBuf<uint8_t>* dvalid, std::string* err) {
+// What the kernels see of a prepared window: its block table and valid[].
+struct GuessWindow {
+  hbam::DevBuf<uint8_t> valid;
+  hbam::DevBuf<hbam::BlockInfo> cut;  // the table with a cut last block's entry after it, when there is one
+  const hbam::BlockInfo* blocks = nullptr;
+  uint32_t nblk = 0;
+  explicit GuessWindow(const hbam::StreamSet* s) : valid(s), cut(s) {}
+};
+
+// Load + locate + inflate + CRC-check the window; valid[k] per block.
+int prepare_window(BamFile& f, uint64_t lo, uint64_t hi, GuessWindow* w, std::string* err) {
   using namespace hbam;
+  hbam::DevBuf<uint8_t>* dvalid = &w->valid;
   int rc = f.load_window(lo, hi, /*free_start=*/true);
   if (rc != kOk) {
     *err = f.error();
@@ -487,7 +497,7 @@ int prepare_window(BamFile& f, uint64_t lo, uint64_t hi, hbam::DevBuf<uint8_t>* 
   Pipeline& p = f.pipe();
   const auto& blk = p.blocks();
   const uint32_t nblk = (uint32_t)blk.size();
-  std::vector<uint8_t> valid(nblk, 0);
+  std::vector<uint8_t> valid(nblk + 1, 0);
   std::vector<uint32_t> dev_idx;
   if (nblk) {
     // inflate errors mark blocks invalid, as a failed seek would
@@ -506,7 +516,25 @@ int prepare_window(BamFile& f, uint64_t lo, uint64_t hi, hbam::DevBuf<uint8_t>* 
     return e == hipSuccess;
   };
   if (!chk(dvalid->reserve(nblk + 1)) || !chk(dlist.reserve(dev_idx.size() + 1))) return kErrDevice;
-  if (nblk && !chk(hipMemcpyAsync(dvalid->p, valid.data(), nblk, hipMemcpyHostToDevice, s))) return kErrDevice;
+  if (!chk(hipMemcpyAsync(dvalid->p, valid.data(), nblk + 1, hipMemcpyHostToDevice, s))) return kErrDevice;
+  w->blocks = p.d_blocks();
+  w->nblk = nblk;
+  // The file ends inside a block: the chain stops before it.  A reader that
+  // gets there finds a header cut short (fewer than 18 bytes) or a truncated
+  // block, not the end of the stream, so the cut block takes an entry of its
+  // own, never valid, that reaches past the end of the file.
+  if (nblk && p.at_eof() && blk.back().coff + blk.back().csize < f.file_size()) {
+    BlockInfo t = BlockInfo();
+    t.coff = blk.back().coff + blk.back().csize;
+    t.ustart = blk.back().ustart + blk.back().isize;
+    t.csize = (uint32_t)std::min<uint64_t>(f.file_size() - t.coff, 0xffff) + 1;
+    if (!chk(w->cut.reserve(nblk + 1)) ||
+        !chk(hipMemcpyAsync(w->cut.p, blk.data(), nblk * sizeof(BlockInfo), hipMemcpyHostToDevice, s)) ||
+        !chk(hipMemcpyAsync(w->cut.p + nblk, &t, sizeof t, hipMemcpyHostToDevice, s)) || !chk(hipStreamSynchronize(s)))
+      return kErrDevice;
+    w->blocks = w->cut.p;
+    w->nblk = nblk + 1;
+  }
   if (!dev_idx.empty()) {  // setCheckCrcs(true): valid[k] = CRC ok
     if (!chk(hipMemcpyAsync(dlist.p, dev_idx.data(), dev_idx.size() * 4, hipMemcpyHostToDevice, s))) return kErrDevice;
     hipLaunchKernelGGL(k_block_crc, dim3((uint32_t)dev_idx.size()), dim3(256), 0, s, p.d_blocks(), dlist.p,
@@ -519,7 +547,7 @@ int prepare_window(BamFile& f, uint64_t lo, uint64_t hi, hbam::DevBuf<uint8_t>* 
 
 // points [a, b) through kernel K; results into out by slot
 template <typename Launch>
-int run_points(BamFile& f, const std::vector<GuessPoint>& pts, size_t a, size_t b, const hbam::DevBuf<uint8_t>& dvalid,
+int run_points(BamFile& f, const std::vector<GuessPoint>& pts, size_t a, size_t b, const GuessWindow& w,
                std::vector<uint64_t>* out, std::string* err, int32_t n_ref, Launch&& launch) {
   using namespace hbam;
   Pipeline& p = f.pipe();
@@ -544,10 +572,10 @@ int run_points(BamFile& f, const std::vector<GuessPoint>& pts, size_t a, size_t 
   GuessEnv E;
   E.file = p.d_file() - p.base();  // absolute file coordinates (the window covers every point's bytes)
   E.flen = f.file_size();
-  E.blocks = p.d_blocks();
-  E.nblk = (uint32_t)p.blocks().size();
+  E.blocks = w.blocks;
+  E.nblk = w.nblk;
   E.u = p.d_u();
-  E.valid = dvalid.p;
+  E.valid = w.valid.p;
   E.n_ref = n_ref;
   launch(E, dbeg.p, dend.p, m, dout.p, dst.p, s);
   if (!chk(hipGetLastError())) return kErrDevice;
@@ -580,11 +608,11 @@ int guess_batch(BamFile& f, const std::vector<uint64_t>& begs, const std::vector
     const uint64_t lim = std::min<uint64_t>(begs[i] + std::min<uint64_t>(ends[i] - begs[i], kMaxBytesRead), f.file_size());
     pts.push_back({begs[i], ends[i], lim, i});
   }
-  DevBuf<uint8_t> dvalid(&f.pipe().streams());
+  GuessWindow win(&f.pipe().streams());
   return for_each_window(f, pts, [&](uint64_t lo, uint64_t hi, size_t a, size_t b) {
-    int rc = prepare_window(f, lo, hi, &dvalid, err);
+    int rc = prepare_window(f, lo, hi, &win, err);
     if (rc != kOk) return rc;
-    return run_points(f, pts, a, b, dvalid, out, err, n_ref < 0 ? f.n_ref() : n_ref,
+    return run_points(f, pts, a, b, win, out, err, n_ref < 0 ? f.n_ref() : n_ref,
                       [](const GuessEnv& E, const uint64_t* db, const uint64_t* de, uint32_t m, uint64_t* dout,
                          int32_t* dst, hipStream_t s) {
                         hipLaunchKernelGGL(k_guess_splits, dim3((m + 63) / 64), dim3(64), 0, s, E, db, de, m, dout,
@@ -612,11 +640,11 @@ int guess_bgzf_batch(BamFile& f, const std::vector<uint64_t>& begs, const std::v
         std::min<uint64_t>(begs[i] + std::min<uint64_t>(ends[i] - begs[i], kBgzfGuessWindow), f.file_size());
     pts.push_back({begs[i], ends[i], lim, i});
   }
-  DevBuf<uint8_t> dvalid(&f.pipe().streams());
+  GuessWindow win(&f.pipe().streams());
   return for_each_window(f, pts, [&](uint64_t lo, uint64_t hi, size_t a, size_t b) {
-    int rc = prepare_window(f, lo, hi, &dvalid, err);
+    int rc = prepare_window(f, lo, hi, &win, err);
     if (rc != kOk) return rc;
-    return run_points(f, pts, a, b, dvalid, out, err, f.n_ref(),
+    return run_points(f, pts, a, b, win, out, err, f.n_ref(),
                       [](const GuessEnv& E, const uint64_t* db, const uint64_t* de, uint32_t m, uint64_t* dout,
                          int32_t*, hipStream_t s) {
                         hipLaunchKernelGGL(k_guess_bgzf_starts, dim3((m + 63) / 64), dim3(64), 0, s, E, db, de, m,

@@ -263,6 +263,8 @@ struct StreamCursor {
       if (pos >= buf_pos + buf.size() || pos < buf_pos) {
         uint64_t want = std::max<uint64_t>(n - *got, 1 << 20);
         int rc = p.read_stream(pos, want, &buf);
+        // a block that does not inflate, past the bytes asked for, is not this read's to report
+        if (rc != kOk && want > n - *got) rc = p.read_stream(pos, n - *got, &buf);
         if (rc != kOk) return rc;
         buf_pos = pos;
         if (buf.empty()) return kOk;
@@ -288,6 +290,20 @@ int BamFile::parse_header() {
   uint64_t w = std::min<uint64_t>(src_.size, std::min<uint64_t>(window_bytes_, 1ull << 20));
   for (;;) {
     int rc = load_window(0, w);
+    if (rc != kOk && w >= src_.size) {
+      // the whole file is in the window and its block chain breaks: if only
+      // the last block is cut short, the header is read from the blocks
+      // before it ([htsjdk] reads a header without looking at the file's end;
+      // the split guessers work on such files); a read that gets to the cut
+      // block reports it
+      const std::string first_err = err_;
+      if (load_window(0, w, /*free_start=*/true) != kOk || pipe_->blocks().size() == 0 ||
+          pipe_->blocks().data()[0].coff != 0) {
+        err_ = first_err;
+        return rc;
+      }
+      rc = kOk;
+    }
     if (rc != kOk) return rc;
     const bool whole = pipe_->at_eof();
     StreamCursor c(*pipe_);

@@ -525,7 +525,10 @@ int Pipeline::locate(bool free_start) {
   empty_blocks_ = 0;
   uint32_t n = 0;
   uint64_t tail = 0;
-  int rc = locate_range(base_, base_ + flen_, !at_eof_, free_start, 0, 0, stream_, &n, &tail);
+  // free start (the split guessers): a last block cut by the end of the file
+  // ends the chain like one cut by an open window's end; the blocks before it
+  // stand, as for a reader that has not got there yet
+  int rc = locate_range(base_, base_ + flen_, !at_eof_ || free_start, free_start, 0, 0, stream_, &n, &tail);
   if (rc != kOk) return rc;
   window_end_ = at_eof_ ? base_ + flen_ : tail;
   if (n && at_eof_ && free_start) window_end_ = hblocks_[n - 1].coff + hblocks_[n - 1].csize;

@@ -204,14 +204,25 @@ class Stream:
         L.orc_free(p)
         return b
 
-    def guess_record_start(self, beg, end, header_n_ref=None):
+    def guess_record_start(self, beg, end, header_n_ref=None, file=None):
+        """file: bytes or a ctypes buffer of the stream's own length (or, for a
+        file cut short, less) to guess over in its place (a damaged copy:
+        orc_open inflates every block, so a file with a broken block cannot
+        be opened; the guesser takes only n_ref from the stream and reads the
+        bytes it is given)."""
         L = lib()
         out = C.c_uint64()
-        if header_n_ref is None:
-            rc = L.orc_guess_record_start(self._h, self._buf, len(self.file), beg, end, C.byref(out))
+        buf, flen = self._buf, len(self.file)
+        if file is not None:
+            if len(file) > flen:
+                raise ValueError("file= is longer than the stream's own file")
+            flen = len(file)
+            buf = C.create_string_buffer(file, flen) if isinstance(file, (bytes, bytearray)) else file
+        n_ref = self.n_ref if header_n_ref is None else header_n_ref
+        if header_n_ref is None and file is None:
+            rc = L.orc_guess_record_start(self._h, buf, flen, beg, end, C.byref(out))
         else:
-            rc = L.orc_guess_record_start_hdr(self._h, self._buf, len(self.file), header_n_ref, beg, end,
-                                              C.byref(out))
+            rc = L.orc_guess_record_start_hdr(self._h, buf, flen, n_ref, beg, end, C.byref(out))
         if rc != 0:
             raise OracleError(rc, L.orc_error(self._h).decode())
         return out.value
