@@ -55,6 +55,7 @@ struct hbam_gpu {
   std::unique_ptr<BamFile> f;
   int device = 0;
   uint64_t window = hadoop_bam::kDefaultWindowBytes;
+  int stringency = HBAM_STRICT;  // of the next hbam_gpu_load
   std::string err;
   hbam::SpanDev span;  // last window of the last run
   hbam::DevBuf<uint8_t> enc;  // hbam_gpu_encode_writables output
@@ -569,6 +570,60 @@ int hbam_encode_writables(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* o
   return HBAM_OK;
 }
 
+int hbam_sort_writables(hbam_ctx* ctx, int32_t order, uint8_t* out, uint64_t cap, uint64_t* offs, uint32_t* perm,
+                        uint64_t* len) {
+  *len = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  hbam::Pipeline& p = ctx->f->pipe();
+  hbam::SpanDev span;
+  if (ctx->last_is_writables || ctx->last_is_query || (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
+    ctx->err = "hbam_sort_writables needs a one-window batch from hbam_decode_span";
+    return HBAM_E_STATE;
+  }
+  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE) {
+    ctx->err = "unknown sort order " + std::to_string(order);
+    return HBAM_E_ARG;
+  }
+  const hadoop_bam::BatchView& h = ctx->batch;
+  const uint64_t n = h.n;
+  if (n >= 0x7fffffffull) {
+    ctx->err = "too many records to sort in one batch";
+    return HBAM_E_ARG;
+  }
+  // the encodings' size from the batch's own host columns: no launch
+  uint64_t bytes = 36 * n;
+  for (uint64_t i = 0; i < n; ++i) bytes += h.rest_len[i];
+  *len = bytes;
+  if (!out) return HBAM_OK;
+  if (cap < bytes) {
+    ctx->err = "output buffer too small for the encoded records";
+    return HBAM_E_ARG;
+  }
+  if (n == 0) {
+    if (offs) offs[0] = 0;
+    return HBAM_OK;
+  }
+  hbam::DevBuf<uint8_t> dst(&p.streams());
+  if (dst.reserve((bytes + 15) & ~15ull) != hipSuccess) {
+    ctx->err = "hipMalloc failed";
+    return HBAM_E_DEVICE;
+  }
+  const int rc = p.sort_writables(span, order, bytes, dst.p);
+  if (rc != HBAM_OK) {
+    ctx->err = p.error();
+    return rc;
+  }
+  hipError_t e = hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, p.stream());
+  if (e == hipSuccess && offs)
+    e = hipMemcpyAsync(offs, p.sort_offsets(), (n + 1) * 8, hipMemcpyDeviceToHost, p.stream());
+  if (e == hipSuccess && perm) e = hipMemcpyAsync(perm, p.sort_perm(), n * 4, hipMemcpyDeviceToHost, p.stream());
+  if (e != hipSuccess || hipStreamSynchronize(p.stream()) != hipSuccess) {
+    ctx->err = "hipMemcpy D2H failed";
+    return HBAM_E_DEVICE;
+  }
+  return HBAM_OK;
+}
+
 int hbam_decode_writables(hbam_ctx* ctx, const void* buf, uint64_t len, const uint64_t* offs, uint64_t n,
                           hbam_batch* out) {
   memset(out, 0, sizeof *out);
@@ -875,6 +930,7 @@ int hbam_gpu_load(hbam_gpu* g, const void* data, uint64_t len) {
   OpenOptions o;
   o.device = g->device;
   o.window_bytes = g->window;
+  o.stringency = g->stringency;
   g->enc.release();  // owned by the old file's pipeline streams
   g->enc.owner = nullptr;
   g->f.reset();
@@ -888,6 +944,15 @@ int hbam_gpu_load(hbam_gpu* g, const void* data, uint64_t len) {
 int hbam_gpu_set_window(hbam_gpu* g, uint64_t window_bytes) {
   g->window = window_bytes ? window_bytes : hadoop_bam::kDefaultWindowBytes;
   if (g->f) g->f->set_window_bytes(g->window);
+  return HBAM_OK;
+}
+
+int hbam_gpu_set_stringency(hbam_gpu* g, int32_t stringency) {
+  if (stringency < HBAM_STRICT || stringency > HBAM_SILENT) {
+    g->err = "unknown validation stringency";
+    return HBAM_E_ARG;
+  }
+  g->stringency = stringency;
   return HBAM_OK;
 }
 
@@ -1053,6 +1118,41 @@ int hbam_gpu_encode_writables(hbam_gpu* g, int32_t iters, float* ms_per_iter, ui
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
+  if (rc != HBAM_OK) {
+    g->err = p.error();
+    return rc;
+  }
+  g->enc_bytes = nb;
+  *bytes = nb;
+  return HBAM_OK;
+}
+
+int hbam_gpu_sort_writables(hbam_gpu* g, int32_t order, int32_t iters, float ms[3], uint64_t* bytes) {
+  ms[0] = ms[1] = ms[2] = 0;
+  *bytes = 0;
+  if (!g->f) return HBAM_E_STATE;
+  hbam::Pipeline& p = g->f->pipe();
+  uint64_t nb = 0;
+  g->enc.owner = &p.streams();
+  int rc = p.encoded_bytes(g->span, &nb);
+  if (rc != HBAM_OK) {
+    g->err = p.error();
+    return rc;
+  }
+  if (g->enc.reserve((nb + 15) & ~15ull) != hipSuccess) {
+    g->err = "hipMalloc failed";
+    return HBAM_E_DEVICE;
+  }
+  rc = p.sort_writables(g->span, order, nb, g->enc.p);  // warm-up (also checks the launches)
+  for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) {
+    float t[3];
+    rc = p.sort_writables(g->span, order, nb, g->enc.p, t);
+    for (int k = 0; k < 3; ++k) ms[k] += t[k] / (float)iters;
+  }
+  if (rc == HBAM_OK && hipStreamSynchronize(p.stream()) != hipSuccess) {
+    g->err = "hipStreamSynchronize failed";
+    return HBAM_E_DEVICE;
+  }
   if (rc != HBAM_OK) {
     g->err = p.error();
     return rc;

@@ -150,6 +150,24 @@ hipError_t launch_long_hash(const uint8_t* u, const uint64_t* rec_pos, const Col
 // (16 B-aligned, room for nbytes rounded up to 16) + bin patches (refID < 0)
 hipError_t launch_wr_encode(const uint8_t* u, uint64_t p0, uint64_t nbytes, const uint64_t* rec_pos,
                             const int32_t* ref_id, const uint16_t* bin, uint64_t n, uint8_t* dst, hipStream_t s);
+// Sorted SAMRecordWritable.write of a span's records (hbam_sort.hip), n < 2^31 - 1.
+// order: kSortKey = ascending signed key, kSortCoordinate = ascending
+// (uint32 refID, pos + 1); both stable.
+enum : int { kSortKey = 0, kSortCoordinate = 1 };
+// temporary storage of the radix sort of n pairs and of the scan over n + 1 lengths
+hipError_t sort_tmp_bytes(uint64_t n, size_t* bytes);
+// perm[j] = the span index of the j-th record in sorted order (word, word_sorted:
+// n u64; len: n u32 = the records' encoded lengths; iota, perm: n u32)
+hipError_t launch_sort_perm(void* tmp, size_t tmp_bytes, const Columns& col, uint64_t n, int order, uint64_t* word,
+                            uint64_t* word_sorted, uint32_t* len, uint32_t* iota, uint32_t* perm, hipStream_t s);
+// doff[j] = the output start of the j-th sorted record, doff[n] = the output's bytes (slen, doff: n + 1 u64)
+hipError_t launch_sort_offsets(void* tmp, size_t tmp_bytes, const uint32_t* len, const uint32_t* perm, uint64_t n,
+                               uint64_t* slen, uint64_t* doff, hipStream_t s);
+// dst[doff[j], doff[j + 1]) = record perm[j]'s bytes at u + rec_pos[perm[j]], indexBin
+// 0 when its refID < 0; total = doff[n]; dst holds total rounded up to 16, u is
+// readable 16 bytes past its last record
+hipError_t launch_sort_gather(const uint8_t* u, const uint64_t* rec_pos, const int32_t* ref_id, const uint32_t* perm,
+                              const uint64_t* doff, uint64_t n, uint64_t total, uint8_t* dst, hipStream_t s);
 // SAMRecordWritable.readFields of n framed values; *bad = min((i << 8) | status)
 hipError_t launch_wr_decode(const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n, const Columns& col,
                             uint64_t* rec_pos, unsigned long long* bad, hipStream_t s);

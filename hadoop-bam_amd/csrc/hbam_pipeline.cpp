@@ -66,7 +66,8 @@ Pipeline::Pipeline(int device) : device_(device) {
   own(own_file_, own_spare_, dblocks_, ref_len_, du_, tokens_[0], tokens_[1], hout_, tables_[0], tables_[1],
       tinfo_[0], tinfo_[1], flist_[0], flist_[1], pstats_, g_, x_, x2_, entry_, base_arr_, summary_, dead_, cand_, sorted_, isz_, ust_, cnt_, flags_,
       errv_, need_, rec_pos_, rec_voff_, rcand_, force_, wcnt_, counters_, list_, scan_tmp_, cols_, long_rec_,
-      long_n_, wbuf_, woffs_, wbad_, scalars_, fuse_);
+      long_n_, wbuf_, woffs_, wbad_, scalars_, fuse_, sort_word_, sort_word2_, sort_slen_, sort_doff_, sort_len_,
+      sort_iota_, sort_perm_, sort_tmp_);
   for (auto& e : ev_) (void)hipEventCreate(&e);
   for (auto& e : sync_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& e : tab_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
@@ -1327,6 +1328,40 @@ int Pipeline::encode_writables(const SpanDev& s, uint64_t bytes, uint8_t* dst) {
   HIPCHK(rb_sync(stream_));
   const uint8_t* src = s.data ? s.data : du_.p;
   HIPCHK(launch_wr_encode(src, first, bytes, s.rec_pos, s.col.ref_id, s.col.bin, s.n, dst, stream_));
+  return kOk;
+}
+
+int Pipeline::sort_writables(const SpanDev& s, int order, uint64_t bytes, uint8_t* dst, float* ms) {
+  if (ms) ms[0] = ms[1] = ms[2] = 0;
+  if (s.n == 0) return kOk;
+  if (!s.col.ref_id || !s.col.key) return fail(kErrState, "span was not decoded in reader mode");
+  if (order != kSortKey && order != kSortCoordinate) return fail(kErrArg, "unknown sort order");
+  if (s.n >= 0x7fffffffull) return fail(kErrArg, "too many records to sort in one batch");
+  HIPCHK(hipSetDevice(device_));
+  const uint64_t n = s.n;
+  size_t tmp = 0;
+  HIPCHK(sort_tmp_bytes(n, &tmp));
+  HIPCHK(sort_tmp_.reserve(tmp));
+  HIPCHK(sort_word_.reserve(n));
+  HIPCHK(sort_word2_.reserve(n));
+  HIPCHK(sort_len_.reserve(n));
+  HIPCHK(sort_iota_.reserve(n));
+  HIPCHK(sort_perm_.reserve(n));
+  HIPCHK(sort_slen_.reserve(n + 1));
+  HIPCHK(sort_doff_.reserve(n + 1));
+  const uint8_t* src = s.data ? s.data : du_.p;
+  if (ms) HIPCHK(hipEventRecord(ev_[4], stream_));
+  HIPCHK(launch_sort_perm(sort_tmp_.p, tmp, s.col, n, order, sort_word_.p, sort_word2_.p, sort_len_.p, sort_iota_.p,
+                          sort_perm_.p, stream_));
+  if (ms) HIPCHK(hipEventRecord(ev_[5], stream_));
+  HIPCHK(launch_sort_offsets(sort_tmp_.p, tmp, sort_len_.p, sort_perm_.p, n, sort_slen_.p, sort_doff_.p, stream_));
+  if (ms) HIPCHK(hipEventRecord(ev_[6], stream_));
+  HIPCHK(launch_sort_gather(src, s.rec_pos, s.col.ref_id, sort_perm_.p, sort_doff_.p, n, bytes, dst, stream_));
+  if (ms) {
+    HIPCHK(hipEventRecord(ev_[7], stream_));
+    HIPCHK(hipEventSynchronize(ev_[7]));
+    for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&ms[k], ev_[4 + k], ev_[5 + k]));
+  }
   return kOk;
 }
 

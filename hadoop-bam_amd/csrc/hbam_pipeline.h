@@ -279,6 +279,16 @@ class Pipeline {
   // to 16).  Record i's encoding starts at rec_pos[i] - rec_pos[0].
   int encoded_bytes(const SpanDev& span, uint64_t* bytes);
   int encode_writables(const SpanDev& span, uint64_t bytes, uint8_t* dst);
+  // encode_writables with the records in sorted order (order: kSortKey /
+  // kSortCoordinate of hbam_launch.h; stable): bytes = encoded_bytes(span).
+  // The order and the output starts stay on the device until the next call:
+  // sort_perm() (n u32, the span index of the j-th output record) and
+  // sort_offsets() (n + 1 u64, the last = bytes).  ms (optional): the HIP-event
+  // times of the sort words + radix sort, the lengths + scan and the gather
+  // (waits for the stream).
+  int sort_writables(const SpanDev& span, int order, uint64_t bytes, uint8_t* dst, float* ms = nullptr);
+  const uint32_t* sort_perm() const { return sort_perm_.p; }
+  const uint64_t* sort_offsets() const { return sort_doff_.p; }
   // SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) of n values
   // framed by offs in host memory (value i = buf[offs[i], offs[i+1]), the
   // last ends at len): SoA columns + keys; out->n stops at the first bad value.
@@ -428,6 +438,10 @@ class Pipeline {
   DevBuf<uint64_t> woffs_;               // readFields: value framing
   DevBuf<unsigned long long> wbad_;      // readFields: first bad value
   DevBuf<uint64_t> scalars_;             // next_pos / digests read back by the host
+  // sort_writables: sort words in / out, sorted lengths, output starts; lengths, iota, order; hipcub storage
+  DevBuf<uint64_t> sort_word_, sort_word2_, sort_slen_, sort_doff_;
+  DevBuf<uint32_t> sort_len_, sort_iota_, sort_perm_;
+  DevBuf<uint8_t> sort_tmp_;
 
   hipEvent_t ev_[8];
   std::vector<hipEvent_t> tev_;     // timing events of overlapped inflate chunks

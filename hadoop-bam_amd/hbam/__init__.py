@@ -123,13 +123,16 @@ _sig("hbam_gpu_destroy", None, [P])
 _sig("hbam_gpu_error", C.c_char_p, [P])
 _sig("hbam_gpu_load", C.c_int, [P, P, u64])
 _sig("hbam_gpu_set_window", C.c_int, [P, u64])
+_sig("hbam_gpu_set_stringency", C.c_int, [P, i32])
 _sig("hbam_gpu_index", C.c_int, [P, i32, C.POINTER(P), C.POINTER(u64), C.POINTER(C.c_float)])
 _sig("hbam_gpu_run", C.c_int, [P, i32, C.POINTER(GpuStats)])
 _sig("hbam_gpu_fetch", C.c_int, [P, P, P, u64])
 _sig("hbam_encode_writables", C.c_int, [P, P, u64, P, C.POINTER(u64)])
+_sig("hbam_sort_writables", C.c_int, [P, i32, P, u64, P, P, C.POINTER(u64)])
 _sig("hbam_decode_writables", C.c_int, [P, P, u64, P, u64, C.POINTER(Batch)])
 _sig("hbam_open_codec", C.c_int, [C.POINTER(Opts), C.POINTER(P)])
 _sig("hbam_gpu_encode_writables", C.c_int, [P, i32, C.POINTER(C.c_float), C.POINTER(u64)])
+_sig("hbam_gpu_sort_writables", C.c_int, [P, i32, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_fetch_encoded", C.c_int, [P, u64, u64, P])
 _sig("hbam_gpu_reload", C.c_int, [P, P, u64, i32, C.POINTER(C.c_float)])
 _sig("hbam_gpu_run_streamed", C.c_int, [P, P, u64, u64, C.POINTER(GpuStats)])
@@ -143,6 +146,8 @@ _sig("hbam_bai_summarize", C.c_int, [P, u64, C.POINTER(BaiSummary)])
 _sig("hbam_bai_query", C.c_int, [P, u64, P, u64, C.POINTER(P), C.POINTER(u64)])
 
 BGZF_EOF = 1
+SORT_KEY, SORT_COORDINATE = 0, 1  # hbam_sort_writables orders
+SORT_ORDERS = {"key": SORT_KEY, "coordinate": SORT_COORDINATE}
 BAI_METADATA = 1  # hbam_build_bai: the pseudo-bins 37450 and the trailing n_no_coor
 HTSJDK_BLOCK_SIZE = 65498  # ISIZE of every full block of test.bam (htsjdk-written)
 
@@ -421,6 +426,25 @@ class BamFile:
         return {"n_ref": h.n_ref, "l_text": h.l_text, "first_record_voff": h.first_record_voff,
                 "file_size": h.file_size, "text": text}
 
+    def header_bytes(self) -> bytes:
+        """The BAM header as a writer takes it (magic, l_text, text, n_ref and
+        the references), rebuilt from hbam_header and hbam_ref."""
+        h = HeaderInfo()
+        rc = _L.hbam_header(self._h, C.byref(h))
+        if rc != OK:
+            raise self._err(rc)
+        text = C.string_at(h.text, h.l_text) if h.l_text else b""
+        out = [b"BAM\x01", len(text).to_bytes(4, "little"), text, h.n_ref.to_bytes(4, "little")]
+        for i in range(h.n_ref):
+            name = C.c_char_p()
+            ln = i32()
+            rc = _L.hbam_ref(self._h, i, C.byref(name), C.byref(ln))
+            if rc != OK:
+                raise self._err(rc)
+            out += [(len(name.value) + 1).to_bytes(4, "little"), name.value, b"\0",
+                    ln.value.to_bytes(4, "little", signed=True)]
+        return b"".join(out)
+
     def file_stats(self):
         """(BGZF blocks, inflated bytes) of the whole file."""
         nb, us = u64(), u64()
@@ -613,6 +637,27 @@ class BamFile:
         if rc != OK:
             raise self._err(rc)
         return out.raw[:total], offs
+
+    def sort_writables(self, order="key"):
+        """encode_writables with the records sorted on the GPU
+        (hbam_sort_writables): order "key" (the shuffle's: ascending signed
+        BAMRecordReader key) or "coordinate" (refID, pos; unplaced last), both
+        stable.  (bytes, offsets[u64, n+1], perm[u32, n]): perm[j] = the batch
+        index of the j-th output record."""
+        o = SORT_ORDERS.get(order, order)
+        n = u64()
+        rc = _L.hbam_sort_writables(self._h, o, None, 0, None, None, C.byref(n))
+        if rc != OK:
+            raise self._err(rc)
+        total = n.value
+        out = C.create_string_buffer(max(total, 1))
+        offs = np.zeros(self._last_n + 1, np.uint64)
+        perm = np.zeros(self._last_n, np.uint32)
+        rc = _L.hbam_sort_writables(self._h, o, out, total, offs.ctypes.data,
+                                    perm.ctypes.data if self._last_n else None, C.byref(n))
+        if rc != OK:
+            raise self._err(rc)
+        return out.raw[:total], offs, perm
 
     def decode_writables(self, buf: bytes, offs, raise_on_error=True):
         return _decode_writables(self._h, buf, offs, raise_on_error)
@@ -826,6 +871,12 @@ class Gpu:
     def set_window(self, window_bytes):
         _L.hbam_gpu_set_window(self._h, window_bytes)
 
+    def set_stringency(self, stringency):
+        """Validation stringency of the files loaded from now on (default STRICT)."""
+        rc = _L.hbam_gpu_set_stringency(self._h, stringency)
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+
     def run(self, timing=False, decode=True, digest=False):
         st = GpuStats()
         flags = (1 if timing else 0) | (0 if decode else 2) | (4 if digest else 0)
@@ -880,6 +931,17 @@ class Gpu:
         if rc != OK:
             raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
         return ms.value, nb.value
+
+    def sort_writables(self, order="key", iters=10):
+        """hbam_gpu_sort_writables of the last run's records into the same
+        device buffer (fetch_encoded reads it), timed over `iters` rounds:
+        ((ms sort, ms offsets, ms gather) per round, bytes)."""
+        ms = (C.c_float * 3)()
+        nb = u64()
+        rc = _L.hbam_gpu_sort_writables(self._h, SORT_ORDERS.get(order, order), iters, ms, C.byref(nb))
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        return (ms[0], ms[1], ms[2]), nb.value
 
     def fetch_encoded(self, pos, length):
         buf = C.create_string_buffer(max(length, 1))

@@ -15,7 +15,13 @@ buffered records' offsets are kept until then and fed to the indexer in order
 granularity-th record), finish(file length) at close (:240-243)."""
 import struct
 
+import numpy as np
+
 from . import HTSJDK_BLOCK_SIZE, bgzf_compress
+
+
+# the empty BGZF block a complete BAM ends with (SAM spec 4.1.2)
+BGZF_EOF_BLOCK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
 class SplittingIndexWriter:
@@ -28,6 +34,10 @@ class SplittingIndexWriter:
         if self.count == 0 or (self.count + 1) % self.granularity == 0:
             self.out.write(struct.pack(">Q", voff))
         self.count += 1
+
+    def skip(self, k):
+        """k records that get no entry: processAlignment k times, nothing written."""
+        self.count += k
 
     def finish(self, input_size):
         self.out.write(struct.pack(">Q", input_size << 16))
@@ -47,7 +57,9 @@ class BamWriter:
         self.buf = bytearray(buffer_blocks * block)
         self.pos = 0                # bytes in the buffer
         self.block_address = 0      # compressed bytes written so far
-        self.pending = []           # buffer offsets of the buffered records (indexer only)
+        # the buffered records in order (indexer only): u >= 0 = a record at
+        # buffer offset u; u < 0 = -u records the index only counts (write_records)
+        self.pending = []
         self.index = SplittingIndexWriter(splitting_bai, granularity) if splitting_bai is not None else None
         if header:
             self._put(header)
@@ -58,9 +70,50 @@ class BamWriter:
             self.pending.append(self.pos)
         self._put(rec)
 
-    def close(self):
-        """close (:131-143): the partial block deflated, no EOF; the index finished."""
+    def write_records(self, enc, offs):
+        """write_record of the n records enc[offs[i]:offs[i+1]] in one go: the
+        same buffering, block cuts and index entries as n single calls, with a
+        copy per buffer fill and an index step per entry instead of per record."""
+        offs = np.asarray(offs, np.uint64).astype(np.int64)
+        enc = memoryview(enc)
+        n, end = len(offs) - 1, int(offs[-1]) if len(offs) else 0
+        cur, i = int(offs[0]) if n > 0 else end, 0
+        while cur < end:
+            k = min(end - cur, len(self.buf) - self.pos)
+            j = int(np.searchsorted(offs[:n], cur + k, side="left"))  # records [i, j) start in this piece
+            if self.index is not None and j > i:
+                self._pend(offs[i:j] - cur + self.pos)
+            self.buf[self.pos:self.pos + k] = enc[cur:cur + k]
+            self.pos += k
+            cur += k
+            i = j
+            if self.pos == len(self.buf):
+                self._deflate(self.pos)
+
+    def _pend(self, at):
+        """Buffer offsets `at` of the next records: the ones the index writes an
+        entry for (ordinal 0 and every granularity-th), the others as counts."""
+        g = self.index.granularity
+        first = self.index.count + sum(1 if u >= 0 else -u for u in self.pending)  # the first one's ordinal
+        o = first + np.arange(len(at), dtype=np.int64)
+        last = -1
+        for h in np.nonzero((o == 0) | ((o + 1) % g == 0))[0]:
+            h = int(h)
+            if h - last > 1:
+                self.pending.append(-(h - last - 1))
+            self.pending.append(int(at[h]))
+            last = h
+        if len(at) - last > 1:
+            self.pending.append(-(len(at) - last - 1))
+
+    def close(self, eof=False):
+        """close (:131-143): the partial block deflated, no EOF; the index finished.
+        eof: the 28-byte BGZF terminator follows (the stock writer leaves that to
+        the merge step), counted in the file length the index ends with."""
         self._deflate(self.pos)
+        if eof:
+            self.out.write(BGZF_EOF_BLOCK)
+            self.block_address += len(BGZF_EOF_BLOCK)
         if self.index is not None:
             self.index.finish(self.block_address)
 
@@ -85,7 +138,10 @@ class BamWriter:
             p += int.from_bytes(z[p + 16:p + 18], "little") + 1
         self.out.write(z)
         for u in self.pending:
-            self.index.process_alignment(starts[u // self.block] << 16 | u % self.block)
+            if u < 0:
+                self.index.skip(-u)
+            else:
+                self.index.process_alignment(starts[u // self.block] << 16 | u % self.block)
         self.pending = []
         self.block_address += len(z)
         self.pos = 0

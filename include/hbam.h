@@ -339,6 +339,36 @@ int hbam_bai_query(const void *bai, uint64_t len, const hbam_interval *iv, uint6
  * HBAM_E_ARG.  A batch from several windows (max_records = 0 over a split
  * longer than a window) -> HBAM_E_STATE: encode bounded batches. */
 int hbam_encode_writables(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *offs, uint64_t *len);
+/* hbam_encode_writables of the last hbam_decode_span batch with the records in
+ * sorted order, sorted and gathered on the GPU (the map-side sort of the
+ * reference's sort job: the shuffle orders records by BAMRecordReader.getKey).
+ * Each record's bytes are exactly what hbam_encode_writables writes for it;
+ * only the order differs.  perm (NULL or n entries) receives the batch index
+ * of the j-th output record, offs (NULL or n+1 entries) the output starts,
+ * offs[n] = *len.  out == NULL only sizes: *len is set, nothing is launched,
+ * offs and perm are left untouched.
+ *   HBAM_SORT_KEY         ascending hbam_batch.key compared as a signed 64-bit
+ *       value (LongWritable.compareTo).  An unmapped read's key is
+ *       Integer.MAX_VALUE << 32 | hash with the int hash sign-extended, so about
+ *       half of the unmapped reads have negative keys and sort first, as in the
+ *       reference.
+ *   HBAM_SORT_COORDINATE  ascending (uint64)(uint32)refID << 32 | (uint32)(pos + 1):
+ *       contigs in dictionary order, refID -1 last, pos -1 first within its
+ *       contig, a placed unmapped read at its position.
+ * Both orders are stable: records with equal sort words keep their batch order.
+ * That tie order is neither htsjdk's SAMRecordCoordinateComparator (which goes
+ * on to strand, read name, flags, ...) nor samtools' strand tie-break; it is a
+ * valid SO:coordinate order under the SAM specification, and the order
+ * hbam_build_bai accepts.
+ * Errors: no file ctx, a last batch from hbam_query_next or
+ * hbam_decode_writables, or a batch from several windows (one call sorts one
+ * window's records: open with a window_bytes that holds the split, or sort
+ * bounded batches) -> HBAM_E_STATE; an unknown order, cap < *len with out set,
+ * or n >= 2^31 - 1 -> HBAM_E_ARG.  n == 0 -> HBAM_OK with *len = 0. */
+#define HBAM_SORT_KEY        0
+#define HBAM_SORT_COORDINATE 1
+int hbam_sort_writables(hbam_ctx *ctx, int32_t order, uint8_t *out, uint64_t cap, uint64_t *offs, uint32_t *perm,
+                        uint64_t *len);
 /* SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) for n serialized
  * values at once: value i = buf[offs[i], offs[i+1]) (the last ends at len), as
  * the shuffle frames them.  Decodes into out like hbam_decode_span (voff =
@@ -474,6 +504,9 @@ int hbam_gpu_load(hbam_gpu *g, const void *data, uint64_t len);
 /* HBM window of the decode (default 4 GiB of compressed bytes): a file larger
  * than the window is decoded window by window. */
 int hbam_gpu_set_window(hbam_gpu *g, uint64_t window_bytes);
+/* Validation stringency of the files loaded from now on (HBAM_STRICT when
+ * never set); an unknown value -> HBAM_E_ARG. */
+int hbam_gpu_set_stringency(hbam_gpu *g, int32_t stringency);
 /* One pass of the hot path over the resident file, first record to EOF:
  * BGZF discovery, inflate, record scan, field decode + keys + voffs, window by
  * window (flags as hbam_decode_span_device). */
@@ -503,6 +536,11 @@ int hbam_gpu_d2d_bandwidth(hbam_gpu *g, uint64_t bytes, int32_t iters, float *gb
  * stream); hbam_gpu_fetch_encoded copies [pos, pos+len) of it to the host. */
 int hbam_gpu_encode_writables(hbam_gpu *g, int32_t iters, float *ms_per_iter, uint64_t *bytes);
 int hbam_gpu_fetch_encoded(hbam_gpu *g, uint64_t pos, uint64_t len, uint8_t *dst);
+/* hbam_sort_writables of the records of the last hbam_gpu_run into the same
+ * device buffer (hbam_gpu_fetch_encoded reads it), iters timed times: ms =
+ * the per-iteration HIP-event times of (sort words + radix sort, lengths +
+ * scan, gather).  For measuring only. */
+int hbam_gpu_sort_writables(hbam_gpu *g, int32_t order, int32_t iters, float ms[3], uint64_t *bytes);
 /* BGZF-compress the inflated stream of the last run (one window) on the GPU
  * with the loaded file's block boundaries (hbam_bgzf_compress semantics;
  * iters timed repetitions, HIP events); the result stays in HBM,

@@ -479,6 +479,34 @@ JNIEXPORT jlong FN(encodeWritables)(JNIEnv *env, jclass c, jlong h, jobject out,
   return (jlong)len;
 }
 
+JNIEXPORT jlong FN(sortWritables)(JNIEnv *env, jclass c, jlong h, jint order, jobject out, jlongArray offs,
+                                  jintArray perm) {
+  uint64_t len = 0;
+  uint8_t *dst = out ? (uint8_t *)(*env)->GetDirectBufferAddress(env, out) : NULL;
+  const uint64_t cap = out ? (uint64_t)(*env)->GetDirectBufferCapacity(env, out) : 0;
+  uint64_t *o = NULL;
+  jsize no = 0;
+  if (out && offs) {
+    no = (*env)->GetArrayLength(env, offs);
+    o = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(no ? no : 1));
+    if (!o) {
+      throw_for(env, HBAM_E_NOMEM, "out of memory");
+      return -1;
+    }
+  }
+  /* perm is written in place (n entries, the caller sized it from the batch) and committed on release */
+  jint *pm = out && perm ? (*env)->GetIntArrayElements(env, perm, NULL) : NULL;
+  int rc = hbam_sort_writables(CTX(h), order, dst, cap, o, (uint32_t *)pm, &len);
+  if (pm) (*env)->ReleaseIntArrayElements(env, perm, pm, 0);
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, hbam_last_error(CTX(h)));
+  } else if (o && no) {
+    (*env)->SetLongArrayRegion(env, offs, 0, no, (const jlong *)o);
+  }
+  free(o);
+  return (jlong)len;
+}
+
 JNIEXPORT jlong FN(openCodec)(JNIEnv *env, jclass c, jint device) {
   hbam_opts o = {device, 0, HBAM_STRICT, 0, 0, 0};
   hbam_ctx *ctx = NULL;

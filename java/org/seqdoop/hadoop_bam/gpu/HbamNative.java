@@ -18,6 +18,7 @@
 //   BAMSplitGuesser.guessNextBAMRecordStart (BAMSplitGuesser.java:108-235) -> guessRecordStarts
 //   BAMInputFormat.getSplits per file (BAMInputFormat.java:222-318, 469-530) -> getSplits
 //   SAMRecordWritable.write / readFields (SAMRecordWritable.java:55-68) -> encodeWritables, decodeWritables
+//   the shuffle's sort on BAMRecordReader.getKey (map side), coordinate order -> sortWritables
 //   BlockCompressedOutputStream under BAMRecordWriter                 -> bgzfCompress
 //
 // Errors: every native method throws the exception the Java method it
@@ -200,6 +201,18 @@ public final class HbamNative {
    * total.  Returns the total (out == null only sizes).
    */
   public static native long encodeWritables(long ctx, ByteBuffer out, long[] offs) throws IOException;
+
+  /** {@link #sortWritables} orders: the shuffle's (signed key) / (refID, pos) with unplaced reads last. */
+  public static final int SORT_KEY = 0, SORT_COORDINATE = 1;
+
+  /**
+   * hbam_sort_writables: encodeWritables with the records of the last decodeSpan
+   * sorted on the GPU (stable; order SORT_KEY or SORT_COORDINATE).  offs (n + 1)
+   * receives the output starts, perm (n) the batch index of each output record;
+   * either may be null.  Returns the total (out == null only sizes).
+   */
+  public static native long sortWritables(long ctx, int order, ByteBuffer out, long[] offs, int[] perm)
+      throws IOException;
 
   /** hbam_open_codec: a device context with no file (reduce side). */
   public static native long openCodec(int device) throws IOException;
