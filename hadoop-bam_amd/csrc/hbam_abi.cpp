@@ -495,6 +495,12 @@ int hbam_inflate_path_counts(hbam_ctx* ctx, uint64_t out[3]) {
   return ctx->f->pipe().inflate_path_counts(out) == 0 ? HBAM_OK : HBAM_E_DEVICE;
 }
 
+int hbam_inflate_narrow_counts(hbam_ctx* ctx, uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  return ctx->f->pipe().inflate_narrow_counts(out) == 0 ? HBAM_OK : HBAM_E_DEVICE;
+}
+
 int hbam_chain_counters(hbam_ctx* ctx, uint64_t out[4]) {
   out[0] = out[1] = out[2] = out[3] = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;

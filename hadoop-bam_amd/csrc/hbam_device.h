@@ -76,19 +76,36 @@ struct HuffTableInfo {
 // list of u32: [r] = blocks handed over in round r (zeroed on the stream
 // before the chunk's first round), [kHuffListHdr + i] = the i-th one's index
 // in the chunk.
-constexpr uint32_t kHuffListHdr = 8;
-static_assert(kInflateRounds <= kHuffListHdr, "one list counter per round");
+// A round after the first runs the lean body twice: 128 lanes wide over the
+// chunk (the narrow instance), which hands the blocks whose window is larger
+// than its stage up to the 256-lane instance through a second list in the
+// same buffer.  That list is kHuffUpSlots sub-lists keyed by block index %
+// kHuffUpSlots, each counter (one per round) on a 128 B line of its own: with
+// every block handed up, appends to one word would serialise.  Sub-list k's
+// entries: [kHuffListHdr + nb + k * ceil(nb / kHuffUpSlots) ..), nb = blocks
+// of the chunk.  The header (both lists' counters) is zeroed by one fill.
+constexpr uint32_t kHuffListRounds = 8;
+constexpr uint32_t kHuffUpCtr = 32;    // word of sub-list 0's counters
+constexpr uint32_t kHuffUpSlots = 16;
+constexpr uint32_t kHuffUpStride = 32;  // words between sub-lists' counters
+constexpr uint32_t kHuffListHdr = kHuffUpCtr + kHuffUpSlots * kHuffUpStride;
+static_assert(kInflateRounds <= kHuffListRounds, "one list counter per round");
+// words of a chunk's list buffer
+constexpr uint64_t huff_list_words(uint64_t nb) { return kHuffListHdr + 2 * nb + kHuffUpSlots; }
 // the fallback's grid: it strides over the list (an empty list costs one
 // small launch, not the ~47 us of a near-empty launch over the chunk)
 constexpr uint32_t kHuffFallbackGrid = 1024;
+constexpr uint32_t kHuffUpGrid = 1280;  // the hand-up launch's, likewise (5 workgroups on each of 256 CUs)
 // Path counters of the last inflate (u32 words, read only on request):
-// block rounds the fallback decoded, and those the lean instance completed,
-// spread over kPathStatSlots words in separate 128 B lines.
+// block rounds the fallback decoded, and those the 256-lane and the narrow
+// lean instance completed, each spread over kPathStatSlots words in separate
+// 128 B lines.
 constexpr uint32_t kPathStatFallback = 0;
 constexpr uint32_t kPathStatLean = 32;
 constexpr uint32_t kPathStatSlots = 16;
 constexpr uint32_t kPathStatStride = 32;
-constexpr uint32_t kPathStatWords = kPathStatLean + kPathStatSlots * kPathStatStride;
+constexpr uint32_t kPathStatNarrow = kPathStatLean + kPathStatSlots * kPathStatStride;
+constexpr uint32_t kPathStatWords = kPathStatNarrow + kPathStatSlots * kPathStatStride;
 
 // Record-chain transition rules.
 enum ChainMode : int {

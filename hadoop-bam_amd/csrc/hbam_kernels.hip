@@ -318,7 +318,8 @@ constexpr int kHuffWaves = kHuffThreads / 64;
 // Phase A runs as two kernels per round.  The lean instance (k_inflate_huff)
 // decodes one DEFLATE block per workgroup from prebuilt tables, with only the
 // round's window of compressed bits staged in LDS, at kLeanWavesPerSimd waves
-// per SIMD; whatever it does not handle goes to the fallback kernel
+// per SIMD (a round after the first: 128 lanes wide, LeanGeom below);
+// whatever it does not handle goes to the fallback kernel
 // (k_huff_fallback), the full body (huff_block) at 4 waves per SIMD, which
 // reads the block from an LDS copy (staged) when the tables + the block fit
 // kHuffStageMaxLds, else straight from HBM/L2 (C4: 7.4 -> 3.9 ms; C2: staged
@@ -1151,6 +1152,8 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 
 // Workgroup-wide helpers for the phase-A workgroup (all threads call them in
 // uniform control flow; each ends with a barrier so `red` can be reused).
+// NW: the workgroup's waves.
+template <int NW = kHuffWaves>
 __device__ __forceinline__ uint32_t wg_any(bool p, uint32_t* red) {
   const uint32_t w = threadIdx.x >> 6;
   const uint64_t b = __ballot(p);
@@ -1158,10 +1161,11 @@ __device__ __forceinline__ uint32_t wg_any(bool p, uint32_t* red) {
   __syncthreads();
   uint32_t r = 0;
 #pragma unroll
-  for (int i = 0; i < kHuffWaves; ++i) r |= red[i];
+  for (int i = 0; i < NW; ++i) r |= red[i];
   __syncthreads();
   return r;
 }
+template <int NW = kHuffWaves>
 __device__ __forceinline__ uint32_t wg_min(uint32_t v, uint32_t* red) {
   const uint32_t w = threadIdx.x >> 6;
 #pragma unroll
@@ -1170,24 +1174,25 @@ __device__ __forceinline__ uint32_t wg_min(uint32_t v, uint32_t* red) {
   __syncthreads();
   uint32_t r = 0xffffffffu;
 #pragma unroll
-  for (int i = 0; i < kHuffWaves; ++i) r = min(r, red[i]);
+  for (int i = 0; i < NW; ++i) r = min(r, red[i]);
   __syncthreads();
   return r;
 }
 // exclusive scans of (u, v) over the workgroup
+template <int NW = kHuffWaves>
 __device__ __forceinline__ void wg_excl_scan2(uint32_t u, uint32_t v, uint32_t* red, uint32_t& eu, uint32_t& ev) {
   const uint32_t w = threadIdx.x >> 6;
   const uint32_t iu = wave_incl_scan(u), iv = wave_incl_scan(v);
   if (lane_id() == 63) {
     red[w] = iu;
-    red[kHuffWaves + w] = iv;
+    red[NW + w] = iv;
   }
   __syncthreads();
   uint32_t ou = 0, ov = 0;
 #pragma unroll
-  for (int i = 0; i < kHuffWaves; ++i) {
+  for (int i = 0; i < NW; ++i) {
     ou += (uint32_t)i < w ? red[i] : 0u;
-    ov += (uint32_t)i < w ? red[kHuffWaves + i] : 0u;
+    ov += (uint32_t)i < w ? red[NW + i] : 0u;
   }
   __syncthreads();
   eu = ou + iu - u;
@@ -1645,14 +1650,16 @@ __global__ __launch_bounds__(64) void k_huff_tables(const uint8_t* __restrict__ 
 }
 
 // Control block: wave 0 -> workgroup (pass parameters) and back (results).
-struct HuffCtl {
+template <int NW>
+struct HuffCtlT {
   uint32_t act;                 // kActDecode / kActDone
   uint32_t B0, out0, tok0;      // all-lane pass: first symbol bit, output / token position
   uint32_t Bend;                // its region end (pass_end; E for a final block)
   uint32_t fe, fx, ftok, fbytes, m3any;  // its result
-  uint32_t xx[kHuffWaves], xe[kHuffWaves];  // exit / event of each wave's last lane
-  uint32_t red[2 * kHuffWaves];
+  uint32_t xx[NW], xe[NW];  // exit / event of each wave's last lane
+  uint32_t red[2 * NW];
 };
+using HuffCtl = HuffCtlT<kHuffWaves>;
 enum : uint32_t { kActDecode = 1, kActDone = 2 };
 constexpr uint32_t kHuffLdsBytes = (sizeof(HuffLds) + 15) & ~15u;
 constexpr uint32_t kHuffCtlBytes = (sizeof(HuffCtl) + 15) & ~15u;
@@ -2044,34 +2051,74 @@ __global__ __launch_bounds__(kHuffThreads, kHuffWavesPerSimd) void k_huff_fallba
 #endif
 constexpr int kLeanWavesPerSimd = HBAM_HUFF_WAVES_PER_SIMD;  // 5: VGPR cap 96, 5 workgroups of <= 32 KB per CU
 constexpr uint32_t kLeanTableBytes = offsetof(HuffLds, cnt_lit);  // lit, litsub, dist, distsub
-constexpr uint32_t kLeanStageCap = kLeanLds - kLeanTableBytes - kHuffCtlBytes;
+// The lean body runs at two widths.  NT = kHuffThreads: kLeanLds per
+// workgroup, every round 0 and the later rounds' hand-up list.  NT =
+// kNarrowThreads: the later rounds' first launch.  A second DEFLATE block is
+// a third of the first one's bits (C2: ~7.3 KB against ~19.5 KB); cut 256
+// ways its slices (~230 bits) are shorter than the 16-32 symbols a walk
+// needs to join the true path, so sync dominates, and two waves pay it
+// instead of four.  Its window fits kNarrowLds, which keeps 20 waves per CU.
+#ifndef HBAM_HUFF_NARROW_LDS
+#define HBAM_HUFF_NARROW_LDS (16 * 1024)
+#endif
+constexpr int kNarrowThreads = 128;
+constexpr uint32_t kNarrowLds = HBAM_HUFF_NARROW_LDS;
+// HBAM_HUFF_NARROW=0: every round at 256 lanes (A/B knob)
+#ifndef HBAM_HUFF_NARROW
+#define HBAM_HUFF_NARROW 1
+#endif
+constexpr bool kHuffNarrow = HBAM_HUFF_NARROW != 0;
+// HBAM_HUFF_MIN_SLICE_BITS: a floor under the slice size (A/B knob: fewer
+// active lanes inside the same workgroup; 0 = off)
+#ifndef HBAM_HUFF_MIN_SLICE_BITS
+#define HBAM_HUFF_MIN_SLICE_BITS 0
+#endif
+constexpr uint32_t kHuffMinSliceBits = HBAM_HUFF_MIN_SLICE_BITS;
+template <int NT>
+struct LeanGeom {
+  static_assert(NT == kHuffThreads || NT == kNarrowThreads, "lean widths");
+  static constexpr int kWaves = NT / 64;
+  static constexpr uint32_t kLds = NT == kHuffThreads ? kLeanLds : kNarrowLds;
+  static constexpr uint32_t kCtlBytes = (sizeof(HuffCtlT<kWaves>) + 15) & ~15u;
+  static constexpr uint32_t kStageCap = kLds - kLeanTableBytes - kCtlBytes;
+};
+constexpr uint32_t kLeanStageCap = LeanGeom<kHuffThreads>::kStageCap;
+constexpr uint32_t kNarrowStageCap = LeanGeom<kNarrowThreads>::kStageCap;
 static_assert(kLeanTableBytes % 16 == 0 && kLeanTableBytes <= kTableImage, "lean tables: a prefix of the table image");
 static_assert(kLeanLds <= 64 * 1024 && kLeanStageCap % 16 == 0 && kLeanStageCap >= 8 * 1024, "lean LDS budget");
+static_assert(kNarrowStageCap % 16 == 0 && kNarrowStageCap >= 8 * 1024 && kNarrowStageCap <= kLeanStageCap,
+              "narrow LDS budget");
 // bits a walk may read past its region end: a lane's exit lies up to one
 // symbol (48 bits) past its stop, and the slow path's reader holds four
 // words from the word of that position on
 constexpr uint32_t kLeanReadPast = 48 + 128;
 
-// One round of block blockIdx.x decoded from its prebuilt tables: the passes
+// One round of the block passed in (blk, ti, timg) from its prebuilt tables: the passes
 // of huff_block over one DEFLATE block (stage, speculate, sync, emit, and the
 // same-tables continuation), every lane taking the (uniform) decisions wave 0
 // takes there.  Handled inline: the end-of-block that leaves the block
 // pending (defer), output overfull (EV_FULLO), and output exactly full
 // (EV_FULLX) where the next code is an end-of-block inside CDATA of a final
-// block -- the end of every well-formed BGZF block.  Returns false, with hout
-// untouched, for everything else: the fallback redoes the round.
+// block -- the end of every well-formed BGZF block.  Returns kLeanDone; or,
+// with hout untouched, kLeanWide (the round's window is larger than this
+// width's stage: a function of blk and ti alone, decided before anything is
+// read) or kLeanOther for everything else: the fallback redoes the round.
 // Bit positions are relative to the 16 B unit the staged window starts at.
-__device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restrict__ file, const BlockInfo& blk,
+enum : int { kLeanDone = 0, kLeanWide = 1, kLeanOther = 2 };
+template <int NT>
+__device__ __forceinline__ int lean_block(uint8_t* smem, const uint8_t* __restrict__ file, const BlockInfo& blk,
                                            uint32_t* __restrict__ tok_out, HuffOut& h, const uint8_t* __restrict__ timg,
                                            const HuffTableInfo& ti, uint32_t isize, uint32_t defer) {
-  if (ti.status != 0) return false;  // no prebuilt tables: stored / fixed block, an anomalous header
-  HuffLds& L = *reinterpret_cast<HuffLds*>(smem + kLeanStageCap);  // (only its leading kLeanTableBytes exist)
-  HuffCtl& C = *reinterpret_cast<HuffCtl*>(smem + kLeanStageCap + kLeanTableBytes);
+  using G = LeanGeom<NT>;
+  using Ctl = HuffCtlT<G::kWaves>;
+  if (ti.status != 0) return kLeanOther;  // no prebuilt tables: stored / fixed block, an anomalous header
+  HuffLds& L = *reinterpret_cast<HuffLds*>(smem + G::kStageCap);  // (only its leading kLeanTableBytes exist)
+  Ctl& C = *reinterpret_cast<Ctl*>(smem + G::kStageCap + kLeanTableBytes);
   const uint32_t tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
   const uint64_t sbyte = blk.coff + 18;  // cdata start
   const uint64_t abase = sbyte & ~15ull;
   const uint32_t Eabs = 8u * ((uint32_t)(sbyte - abase) + (blk.csize - 26));  // end of CDATA
-  if (ti.B0 > Eabs) return false;
+  if (ti.B0 > Eabs) return kLeanOther;
   const bool final_blk = ti.final_blk != 0;
   const uint32_t est = ti.est_bits;
   const uint32_t bend_abs = pass_end(ti.B0, est, final_blk, Eabs);
@@ -2080,7 +2127,7 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
   const uint32_t q0 = min(ti.B0 >> 7, nq_all);
   const uint32_t q1 = min(((bend_abs + kLeanReadPast) >> 7) + 1, nq_all);
   const uint32_t nq = q1 > q0 ? q1 - q0 : 0u;
-  if (nq * 16u > kLeanStageCap) return false;  // a window larger than the stage
+  if (nq * 16u > G::kStageCap) return NT == kNarrowThreads ? kLeanWide : kLeanOther;  // a window larger than the stage
   {  // stage the window and the tables (global -> LDS without registers, as huff_block)
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(file + abase) + q0;
     const uint4* __restrict__ tsrc = reinterpret_cast<const uint4*>(timg);
@@ -2089,9 +2136,9 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
     constexpr uint32_t nt = kLeanTableBytes / 16;
     typedef __attribute__((address_space(3))) void* lds_vp;
     typedef __attribute__((address_space(1))) void* gbl_vp;
-    for (uint32_t u0 = 64 * wave; u0 < nq; u0 += kHuffThreads)
+    for (uint32_t u0 = 64 * wave; u0 < nq; u0 += NT)
       if (u0 + lane < nq) __builtin_amdgcn_global_load_lds((gbl_vp)(src + u0 + lane), (lds_vp)(sdst + u0), 16, 0, 0);
-    for (uint32_t u0 = 64 * wave; u0 < nt; u0 += kHuffThreads)
+    for (uint32_t u0 = 64 * wave; u0 < nt; u0 += NT)
       if (u0 + lane < nt) __builtin_amdgcn_global_load_lds((gbl_vp)(tsrc + u0 + lane), (lds_vp)(tdst + u0), 16, 0, 0);
   }
   __syncthreads();
@@ -2106,9 +2153,9 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
   for (;;) {
     // ---- all-lane decode of [B0, Bend)
     const uint32_t R = Bend > B0 ? Bend - B0 : 0u;
-    const uint32_t S = (R + kHuffThreads - 1) / kHuffThreads;
+    const uint32_t S = max((R + NT - 1) / NT, kHuffMinSliceBits);
     uint32_t a = min(B0 + tid * S, Bend);
-    const uint32_t stop = tid == kHuffThreads - 1 ? Bend : min(B0 + (tid + 1) * S, Bend);
+    const uint32_t stop = tid == NT - 1 ? Bend : min(B0 + (tid + 1) * S, Bend);
     MergePts mp;
     uint32_t mj = 0, x, nt, nb;
     const uint32_t mf = S < kMergeTinyBits ? kMergeFirst / 4 : S < kMergeShortBits ? kMergeFirst / 2 : kMergeFirst;
@@ -2126,7 +2173,7 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
         pev = C.xe[wave - 1];
       }
       const bool need = tid > 0 && pev == EV_STOP && px != a;
-      if (!wg_any(need, C.red)) break;
+      if (!wg_any<G::kWaves>(need, C.red)) break;
       if (need) {
         a = px;
         uint32_t rx, rnt, rnb;
@@ -2145,16 +2192,16 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
         }
       }
     }
-    const uint32_t lend0 = wg_min(ev != EV_STOP ? tid : 0xffffffffu, C.red);
-    const uint32_t lend = lend0 == 0xffffffffu ? (uint32_t)kHuffThreads - 1 : lend0;
+    const uint32_t lend0 = wg_min<G::kWaves>(ev != EV_STOP ? tid : 0xffffffffu, C.red);
+    const uint32_t lend = lend0 == 0xffffffffu ? (uint32_t)NT - 1 : lend0;
     const bool valid = tid <= lend;
     uint32_t toff, boff;
-    wg_excl_scan2(valid ? nt : 0u, valid ? nb : 0u, C.red, toff, boff);
+    wg_excl_scan2<G::kWaves>(valid ? nt : 0u, valid ? nb : 0u, C.red, toff, boff);
     uint32_t x3 = a, nt3 = 0, nb3 = 0, ev3 = EV_STOP;
     if (valid)
       ev3 = lane_decode<LD_EMIT, true>(L, W, a, stop, E, x3, nt3, nb3, mp, mj, tok_out + ntok + toff, outpos + boff,
                                        isize);
-    const uint32_t m3 = wg_min((valid && ev3 != EV_STOP) ? tid : 0xffffffffu, C.red);
+    const uint32_t m3 = wg_min<G::kWaves>((valid && ev3 != EV_STOP) ? tid : 0xffffffffu, C.red);
     const uint32_t f = m3 != 0xffffffffu ? m3 : lend;
     if (tid == f) {
       C.fe = ev3;
@@ -2171,17 +2218,17 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
     if (!m3any) {
       // the pass ended at its region end inside the block: go on with the
       // same tables over the next stretch, if it is staged
-      if (!(Bend < E && fxs < E && outpos < isize)) return false;
+      if (!(Bend < E && fxs < E && outpos < isize)) return kLeanOther;
       const uint32_t bnext = min(E, fxs + (est >> 2) + 4096u);
-      if (bnext + kLeanReadPast > read_end) return false;
+      if (bnext + kLeanReadPast > read_end) return kLeanOther;
       B0 = fxs;
       Bend = bnext;
       continue;
     }
     if (fe == EV_EOB) {
-      if (final_blk || !defer) return false;  // an early end (error), or a header for this round
+      if (final_blk || !defer) return kLeanOther;  // an early end (error), or a header for this round
       h = HuffOut{ntok, kHuffPending, fxs + bias, outpos};  // the next header is the next round's
-      return true;
+      return kLeanDone;
     }
     if (fe == EV_FULLX) {  // zlib's lookahead: the final block's end-of-block, inside CDATA
       const uint32_t wd = fxs >> 5;
@@ -2191,25 +2238,28 @@ __device__ __forceinline__ bool lean_block(uint8_t* smem, const uint8_t* __restr
         e = L.litsub[min((e & 0xffffu) + __builtin_amdgcn_ubfe(lo, kLitRoot, (e >> 16) & 15u),
                          (uint32_t)kLitSubCap - 1)];
       e = rfl(e);
-      if (!final_blk || (e >> 26) != K_EOB || fxs + ((e >> 16) & 31) > E) return false;
+      if (!final_blk || (e >> 26) != K_EOB || fxs + ((e >> 16) & 31) > E) return kLeanOther;
     } else if (fe != EV_FULLO) {
-      return false;  // an error event, input exhausted, a canonical-decode entry
+      return kLeanOther;  // an error event, input exhausted, a canonical-decode entry
     }
     h = HuffOut{ntok, kOk, 0u, outpos};
-    return true;
+    return kLeanDone;
   }
 }
 
-// Phase A, lean instance: one 256-thread workgroup per BGZF block of the
-// chunk, one DEFLATE block per round.  A block whose round it does not handle
-// is appended to flist for k_huff_fallback (launched behind it).  pstats
-// counts the rounds it completed, spread over kPathStatSlots words.
-__global__ __launch_bounds__(kHuffThreads, kLeanWavesPerSimd) void k_inflate_huff(
-    const uint8_t* __restrict__ file, const BlockInfo* __restrict__ blocks, uint32_t b0, uint64_t chunk_ustart,
-    uint32_t* __restrict__ tokens, HuffOut* __restrict__ hout, const uint8_t* __restrict__ tables,
-    const HuffTableInfo* __restrict__ tinfo, uint32_t round, uint32_t defer, uint32_t* flist, uint32_t* pstats) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[kLeanLds];
-  const uint32_t bi = b0 + blockIdx.x;
+// One round of block bx of the chunk by the lean body at width NT.  A block
+// whose round it does not handle is appended to flist for k_huff_fallback
+// (launched behind it); the narrow width appends one whose window is larger
+// than its stage to the hand-up list instead (nb: blocks of the chunk).
+// pstats counts the rounds completed, spread over kPathStatSlots words.
+template <int NT>
+__device__ __forceinline__ void lean_round(uint8_t* smem, const uint8_t* __restrict__ file,
+                                           const BlockInfo* __restrict__ blocks, uint32_t b0, uint64_t chunk_ustart,
+                                           uint32_t* __restrict__ tokens, HuffOut* __restrict__ hout,
+                                           const uint8_t* __restrict__ tables, const HuffTableInfo* __restrict__ tinfo,
+                                           uint32_t round, uint32_t defer, uint32_t* flist, uint32_t* pstats,
+                                           uint32_t bx, uint32_t nb) {
+  const uint32_t bi = b0 + bx;
   const BlockInfo blk = blocks[bi];
   const uint32_t isize = blk.isize;
   if (isize == 0) {  // inflate(buf,off,0) returns 0 without reading: nothing to validate
@@ -2221,16 +2271,54 @@ __global__ __launch_bounds__(kHuffThreads, kLeanWavesPerSimd) void k_inflate_huf
     h = hout[bi];
     if (h.status != kHuffPending) return;
   }
-  const HuffTableInfo ti = tinfo[blockIdx.x];
-  const bool done = lean_block(smem, file, blk, tokens + (blk.ustart - chunk_ustart), h,
-                               tables + (uint64_t)blockIdx.x * kTableImage, ti, isize, defer);
+  const HuffTableInfo ti = tinfo[bx];
+  const int res = lean_block<NT>(smem, file, blk, tokens + (blk.ustart - chunk_ustart), h,
+                                 tables + (uint64_t)bx * kTableImage, ti, isize, defer);
   if (threadIdx.x == 0) {
-    if (done) {
+    constexpr uint32_t stat = NT == kNarrowThreads ? kPathStatNarrow : kPathStatLean;
+    if (res == kLeanDone) {
       hout[bi] = h;
-      atomicAdd(&pstats[kPathStatLean + (blockIdx.x % kPathStatSlots) * kPathStatStride], 1u);
+      atomicAdd(&pstats[stat + (bx % kPathStatSlots) * kPathStatStride], 1u);
+    } else if (NT == kNarrowThreads && res == kLeanWide) {
+      const uint32_t k = bx % kHuffUpSlots, cap = (nb + kHuffUpSlots - 1) / kHuffUpSlots;
+      const uint32_t i = atomicAdd(&flist[kHuffUpCtr + k * kHuffUpStride + round], 1u);
+      if (i < cap) flist[kHuffListHdr + nb + k * cap + i] = bx;
     } else {
-      flist[kHuffListHdr + atomicAdd(&flist[round], 1u)] = blockIdx.x;
+      flist[kHuffListHdr + atomicAdd(&flist[round], 1u)] = bx;
     }
+  }
+}
+
+// Phase A, lean instance: one workgroup of NT lanes per BGZF block, one
+// DEFLATE block per round.  NT = 256 over the chunk in round 0; in a later
+// round NT = 128 over the chunk, then NT = 256, LIST, a fixed grid striding
+// over the blocks the narrow launch handed up (grid x = nb otherwise).
+template <int NT, bool LIST>
+__global__ __launch_bounds__(NT, kLeanWavesPerSimd) void k_inflate_huff(
+    const uint8_t* __restrict__ file, const BlockInfo* __restrict__ blocks, uint32_t b0, uint64_t chunk_ustart,
+    uint32_t* __restrict__ tokens, HuffOut* __restrict__ hout, const uint8_t* __restrict__ tables,
+    const HuffTableInfo* __restrict__ tinfo, uint32_t round, uint32_t defer, uint32_t* flist, uint32_t* pstats,
+    uint32_t nb) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[LeanGeom<NT>::kLds];
+  if (!LIST) {
+    lean_round<NT>(smem, file, blocks, b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, pstats,
+                   blockIdx.x, nb);
+    return;
+  }
+  // one index space over the sub-lists, entry i of sub-list k at i * slots + k
+  // (the sub-lists are about equally long), so the grid shares the blocks evenly
+  const uint32_t cap = (nb + kHuffUpSlots - 1) / kHuffUpSlots;
+  uint32_t nmax = 0;
+  for (uint32_t k = 0; k < kHuffUpSlots; ++k) nmax = max(nmax, flist[kHuffUpCtr + k * kHuffUpStride + round]);
+  nmax = min(rfl(nmax), cap);
+  for (uint32_t j = blockIdx.x; j < nmax * kHuffUpSlots; j += gridDim.x) {
+    const uint32_t k = j % kHuffUpSlots, i = j / kHuffUpSlots;
+    if (i >= rfl(flist[kHuffUpCtr + k * kHuffUpStride + round])) continue;
+    const uint32_t bx = rfl(flist[kHuffListHdr + nb + k * cap + i]);
+    if (bx < nb)
+      lean_round<NT>(smem, file, blocks, b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, pstats,
+                     bx, nb);
+    __syncthreads();  // the next block's staging overwrites this one's LDS
   }
 }
 
@@ -4353,15 +4441,32 @@ hipError_t launch_inflate_huff_prebuilt(const uint8_t* file, const BlockInfo* bl
                                         const uint8_t* tables, const HuffTableInfo* tinfo, uint32_t round,
                                         uint32_t defer, uint32_t* flist, uint32_t* pstats, hipStream_t s) {
   if (nb == 0) return hipSuccess;
-  // the lean instance over the chunk, then the fallback over the blocks it handed over
-  hipLaunchKernelGGL(k_inflate_huff, dim3(nb), dim3(kHuffThreads), 0, s, file, blocks, b0, chunk_ustart, tokens,
-                     hout, tables, tinfo, round, defer, flist, pstats);
+  // the lean instance over the chunk (a later round: 128 lanes wide, then the
+  // 256-lane one over the blocks handed up, a grid under half the chunk's so
+  // that a profile shows one full-size launch per round), then the fallback
+  // over the blocks handed over
+  if (round == 0 || !kHuffNarrow) {
+    hipLaunchKernelGGL((k_inflate_huff<kHuffThreads, false>), dim3(nb), dim3(kHuffThreads), 0, s, file, blocks, b0,
+                       chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, pstats, nb);
+  } else {
+    hipLaunchKernelGGL((k_inflate_huff<kNarrowThreads, false>), dim3(nb), dim3(kNarrowThreads), 0, s, file, blocks,
+                       b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, pstats, nb);
+    const uint32_t up_grid = std::max(1u, std::min((nb - 1) / 2, kHuffUpGrid));
+    hipLaunchKernelGGL((k_inflate_huff<kHuffThreads, true>), dim3(up_grid), dim3(kHuffThreads), 0, s, file, blocks,
+                       b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, pstats, nb);
+  }
   hipLaunchKernelGGL(k_huff_fallback, dim3(std::min(nb, kHuffFallbackGrid)), dim3(kHuffThreads), 0, s, file, blocks,
                      b0, chunk_ustart, tokens, hout, tables, tinfo, round, defer, flist, nb, pstats);
   return hipGetLastError();
 }
 hipError_t huff_lean_occupancy(int* workgroups_per_cu) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, k_inflate_huff, kHuffThreads, 0);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, k_inflate_huff<kHuffThreads, false>,
+                                                      kHuffThreads, 0);
+}
+hipError_t huff_narrow_occupancy(int* workgroups_per_cu, uint32_t* stage_cap_bytes) {
+  *stage_cap_bytes = kNarrowStageCap;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, k_inflate_huff<kNarrowThreads, false>,
+                                                      kNarrowThreads, 0);
 }
 hipError_t launch_inflate_lz77(const BlockInfo* blocks, uint32_t b0, uint32_t nb, uint64_t chunk_ustart,
                                const uint32_t* tokens, const HuffOut* hout, uint8_t* u, hipStream_t s) {

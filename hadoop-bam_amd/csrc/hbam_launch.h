@@ -84,15 +84,20 @@ hipError_t launch_huff_tables(const uint8_t* file, const BlockInfo* blocks, uint
                               hipStream_t s);
 // (defer: stop a block before its next DEFLATE header, kHuffPending, for
 // the next round; the last round decodes every remaining header inline)
-// Two launches: the lean instance over the chunk, then the fallback over the
-// blocks it handed over.  flist: the chunk's hand-over list (kHuffListHdr + nb
-// words, header zeroed before round 0); pstats: kPathStatWords path counters.
+// Round 0, two launches: the lean instance over the chunk, then the fallback
+// over the blocks it handed over.  A later round, three: the lean instance
+// 128 lanes wide over the chunk, the 256-lane one over the blocks whose window
+// the narrow stage does not hold, the fallback.  flist: the chunk's lists
+// (huff_list_words(nb) words, the kHuffListHdr header words zeroed before
+// round 0); pstats: kPathStatWords path counters.
 hipError_t launch_inflate_huff_prebuilt(const uint8_t* file, const BlockInfo* blocks, uint32_t b0, uint32_t nb,
                                         uint64_t chunk_ustart, uint32_t* tokens, HuffOut* hout,
                                         const uint8_t* tables, const HuffTableInfo* tinfo, uint32_t round,
                                         uint32_t defer, uint32_t* flist, uint32_t* pstats, hipStream_t s);
 // resident workgroups per CU the runtime reports for the lean instance
 hipError_t huff_lean_occupancy(int* workgroups_per_cu);
+// the same for the narrow instance, and the bytes of window its stage holds
+hipError_t huff_narrow_occupancy(int* workgroups_per_cu, uint32_t* stage_cap_bytes);
 hipError_t launch_inflate_lz77(const BlockInfo* blocks, uint32_t b0, uint32_t nb, uint64_t chunk_ustart,
                                const uint32_t* tokens, const HuffOut* hout, uint8_t* u, hipStream_t s);
 hipError_t launch_chain(const ChainArgs& a, int mode, int stage, hipStream_t s);

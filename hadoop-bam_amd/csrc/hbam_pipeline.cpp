@@ -349,8 +349,25 @@ int Pipeline::inflate_path_counts(uint64_t out[3]) {
   std::vector<uint32_t> st(kPathStatWords);
   HIPCHK(hipStreamSynchronize(stream_));
   HIPCHK(hipMemcpy(st.data(), pstats_.p, kPathStatWords * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  for (uint32_t k = 0; k < kPathStatSlots; ++k) out[0] += st[kPathStatLean + k * kPathStatStride];
+  for (uint32_t k = 0; k < kPathStatSlots; ++k)
+    out[0] += st[kPathStatLean + k * kPathStatStride] + st[kPathStatNarrow + k * kPathStatStride];
   out[1] = st[kPathStatFallback];
+  return kOk;
+}
+
+int Pipeline::inflate_narrow_counts(uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  HIPCHK(hipSetDevice(device_));
+  int wgs = 0;
+  uint32_t cap = 0;
+  HIPCHK(huff_narrow_occupancy(&wgs, &cap));
+  out[1] = (uint64_t)wgs;
+  out[2] = cap;
+  if (!pstats_.p) return kOk;  // nothing inflated yet
+  std::vector<uint32_t> st(kPathStatSlots * kPathStatStride);
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipMemcpy(st.data(), pstats_.p + kPathStatNarrow, st.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (uint32_t k = 0; k < kPathStatSlots; ++k) out[0] += st[k * kPathStatStride];
   return kOk;
 }
 
@@ -561,7 +578,7 @@ int Pipeline::run_streamed(const uint8_t* data, uint64_t len, uint64_t piece, ui
   for (int i = 0; i < 2; ++i) {
     HIPCHK(tables_[i].reserve((uint64_t)kInflateChunkBlocks * kHuffTableImage));
     HIPCHK(tinfo_[i].reserve(kInflateChunkBlocks));
-    HIPCHK(flist_[i].reserve(kHuffListHdr + kInflateChunkBlocks));
+    HIPCHK(flist_[i].reserve(huff_list_words(kInflateChunkBlocks)));
   }
   HIPCHK(pstats_.reserve(kPathStatWords));
   HIPCHK(streams_.sync());
@@ -691,7 +708,7 @@ int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool joi
       HIPCHK(tokens_[i].reserve(max_u + 16));  // phase B reads tokens as uint4
       HIPCHK(tables_[i].reserve(max_nb * kHuffTableImage));
       HIPCHK(tinfo_[i].reserve(max_nb));
-      HIPCHK(flist_[i].reserve(kHuffListHdr + max_nb));
+      HIPCHK(flist_[i].reserve(huff_list_words(max_nb)));
     }
     HIPCHK(pstats_.reserve(kPathStatWords));
     HIPCHK(hipMemsetAsync(pstats_.p, 0, kPathStatWords * sizeof(uint32_t), stream_));

@@ -322,10 +322,14 @@ class Pipeline {
   // (the sum of HuffOut::ntok; a synchronous read, for measurements)
   int inflate_tokens(uint64_t* n);
   // Phase A's paths in the last inflate (a synchronous read, for
-  // measurements): out[0] = block rounds the lean instance decoded, out[1] =
-  // block rounds it handed to the fallback, out[2] = resident workgroups per
-  // CU the runtime reports for the lean instance
+  // measurements): out[0] = block rounds the lean instance decoded (either
+  // width), out[1] = block rounds it handed to the fallback, out[2] = resident
+  // workgroups per CU the runtime reports for the 256-lane lean instance
   int inflate_path_counts(uint64_t out[3]);
+  // The narrow (128-lane) lean instance's share: out[0] = block rounds it
+  // decoded, out[1] = its resident workgroups per CU as the runtime reports
+  // them, out[2] = the bytes of window its stage holds
+  int inflate_narrow_counts(uint64_t out[3]);
   // The record chain's rare paths since the open (a synchronous read, for
   // tests): out[0] = blocks handed to k_rec_search, out[1] = blocks the link
   // check re-walked from a forced entry, out[2] = stray walks it dropped,

@@ -99,6 +99,7 @@ _sig("hbam_query_next", C.c_int, [P, u64, C.POINTER(Batch)])
 _sig("hbam_pipeline_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_token_count", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_path_counts", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_inflate_narrow_counts", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_chain_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_file_stats", C.c_int, [P, C.POINTER(u64), C.POINTER(u64)])
 _sig("hbam_bytes_read", C.c_int, [P, C.POINTER(u64)])
@@ -499,6 +500,17 @@ class BamFile:
         the lean kernel's resident workgroups per CU (hbam_inflate_path_counts)."""
         v = (u64 * 3)()
         rc = _L.hbam_inflate_path_counts(self._h, v)
+        if rc != OK:
+            raise self._err(rc)
+        return int(v[0]), int(v[1]), int(v[2])
+
+    def inflate_narrow_counts(self):
+        """(narrow, resident, stage_cap): block decode rounds of the last
+        inflate that the lean kernel's 128-lane width decoded (part of
+        inflate_path_counts()[0]), its resident workgroups per CU, and the
+        bytes of window its stage holds (hbam_inflate_narrow_counts)."""
+        v = (u64 * 3)()
+        rc = _L.hbam_inflate_narrow_counts(self._h, v)
         if rc != OK:
             raise self._err(rc)
         return int(v[0]), int(v[1]), int(v[2])

@@ -459,13 +459,22 @@ int hbam_inflate_token_count(hbam_ctx *ctx, uint64_t *tokens);
 
 /* Which of inflate phase A's two kernels decoded the ctx's last inflate,
  * counted per block and decode round (a BGZF block of two DEFLATE blocks
- * takes two rounds): out[0] block rounds the lean instance decoded, out[1]
- * block rounds it handed to the fallback kernel, out[2] the resident
- * workgroups per CU the runtime reports for the lean instance (its answer:
- * a process that has a second copy of the HIP runtime loaded can be told
- * less than the hardware runs).  A measurement helper (no reference
- * counterpart); synchronous, the counters are read only here. */
+ * takes two rounds): out[0] block rounds the lean instance decoded (at either
+ * of its widths), out[1] block rounds it handed to the fallback kernel,
+ * out[2] the resident workgroups per CU the runtime reports for the 256-lane
+ * lean instance (its answer: a process that has a second copy of the HIP
+ * runtime loaded can be told less than the hardware runs).  A measurement
+ * helper (no reference counterpart); synchronous, the counters are read only
+ * here. */
 int hbam_inflate_path_counts(hbam_ctx *ctx, uint64_t out[3]);
+
+/* The share of the lean instance's 128-lane width, which decodes the rounds
+ * after a block's first: out[0] block rounds it decoded in the ctx's last
+ * inflate (included in hbam_inflate_path_counts' out[0]), out[1] its resident
+ * workgroups per CU as the runtime reports them, out[2] the bytes of
+ * compressed window its stage holds (a round with a larger window goes to the
+ * 256-lane width).  A measurement helper; synchronous. */
+int hbam_inflate_narrow_counts(hbam_ctx *ctx, uint64_t out[3]);
 
 /* Which rare paths the ctx's record chain took, cumulative since the open
  * over every call (hbam_pipeline_counters counts spans and rounds; these
