@@ -7,6 +7,8 @@
 //   fresh: deflateInit2 per block (htslib bgzf, tools/gen_synth_bam.c)
 // Usage: deflate_check [file ...]   (files are cut into 65498/65280/... blocks;
 // without files: built-in random / repetitive / text / short-block cases).
+//        deflate_check --blocks PAYLOAD LENS LEVEL[,LEVEL...]   (the payload file
+// cut into the block lengths the text file LENS lists, at each level)
 // Prints one line per case and "ALL OK" when everything matched.
 #include <zlib.h>
 
@@ -85,8 +87,77 @@ static std::vector<uint32_t> cut(uint64_t total, uint32_t bs) {
   return s;
 }
 
+static bool read_file(const char* path, std::vector<uint8_t>* b) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  uint8_t buf[1 << 16];
+  size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) b->insert(b->end(), buf, buf + n);
+  fclose(f);
+  return true;
+}
+
+// --blocks PAYLOAD LENS LEVEL[,LEVEL...]: the payload cut as the text file LENS
+// says (block lengths, whitespace-separated, each <= 65536, summing to the
+// payload), at each level, in both lifecycles
+static int blocks_mode(const char* payload, const char* lens_path, const char* levels) {
+  std::vector<uint8_t> d, lt;
+  if (!read_file(payload, &d) || !read_file(lens_path, &lt)) {
+    printf("cannot read %s or %s\n", payload, lens_path);
+    return 2;
+  }
+  lt.push_back(0);
+  std::vector<uint32_t> sizes;
+  uint64_t tot = 0;
+  for (char* p = reinterpret_cast<char*>(lt.data());;) {
+    char* e;
+    const unsigned long v = strtoul(p, &e, 10);
+    if (e == p) {
+      while (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r') ++p;
+      if (*p) {
+        printf("bad block length at '%.16s'\n", p);
+        return 2;
+      }
+      break;
+    }
+    if (v > 65536) {
+      printf("block length %lu above 65536\n", v);
+      return 2;
+    }
+    sizes.push_back((uint32_t)v);
+    tot += v;
+    p = e;
+  }
+  if (tot != d.size()) {
+    printf("block lengths sum to %llu, payload has %zu bytes\n", (unsigned long long)tot, d.size());
+    return 2;
+  }
+  int bad = 0, n = 0;
+  for (const char* p = levels; *p;) {
+    char* e;
+    const long level = strtol(p, &e, 10);
+    if (e == p || level < 1 || level > 9 || (*e && *e != ',')) {
+      printf("levels: 1..9, comma-separated\n");
+      return 2;
+    }
+    bad += run_case(payload, d, sizes, (int)level, false);
+    bad += run_case(payload, d, sizes, (int)level, true);
+    ++n;
+    p = *e ? e + 1 : e;
+  }
+  printf(bad || !n ? "FAILED (%d)\n" : "ALL OK\n", bad);
+  return bad || !n ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   build_tables(&g_t);
+  if (argc > 1 && strcmp(argv[1], "--blocks") == 0) {
+    if (argc != 5) {
+      printf("usage: deflate_check --blocks PAYLOAD LENS LEVEL[,LEVEL...]\n");
+      return 2;
+    }
+    return blocks_mode(argv[2], argv[3], argv[4]);
+  }
   int bad = 0;
   std::vector<std::pair<std::string, std::vector<uint8_t>>> inputs;
   for (int i = 1; i < argc; ++i) {

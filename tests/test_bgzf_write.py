@@ -91,7 +91,7 @@ def _cases():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("level", [0, 1, 2, 3, 4, 5, 6, 9])
+@pytest.mark.parametrize("level", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9])
 def test_gpu_vs_oracle_levels(level):
     import hbam
     for name, d in _cases().items():
