@@ -483,6 +483,32 @@ int hbam_pipeline_counters(hbam_ctx* ctx, uint64_t out[5]) {
   return HBAM_OK;
 }
 
+namespace {
+void set_locate(BamFile& f, uint64_t seg_bytes, uint32_t cap_limit) {
+  hbam::Pipeline& p = f.pipe();
+  if (seg_bytes == HBAM_LOCATE_SEG_DEFAULT) {
+    seg_bytes = hbam::kLocateSegBytes;
+    if (const char* e = getenv("HBAM_LOCATE_SEG")) seg_bytes = strtoull(e, nullptr, 0);
+  }
+  p.set_locate(seg_bytes, cap_limit);
+  f.invalidate_window();
+}
+}  // namespace
+
+int hbam_locate_counters(hbam_ctx* ctx, uint64_t out[2]) {
+  out[0] = out[1] = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  out[0] = ctx->f->pipe().locate_anchored();
+  out[1] = ctx->f->pipe().locate_declined();
+  return HBAM_OK;
+}
+
+int hbam_set_locate(hbam_ctx* ctx, uint64_t seg_bytes, uint32_t cap_limit) {
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  set_locate(*ctx->f, seg_bytes, cap_limit);
+  return HBAM_OK;
+}
+
 int hbam_inflate_token_count(hbam_ctx* ctx, uint64_t* tokens) {
   *tokens = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
@@ -959,6 +985,23 @@ int hbam_gpu_set_stringency(hbam_gpu* g, int32_t stringency) {
     return HBAM_E_ARG;
   }
   g->stringency = stringency;
+  return HBAM_OK;
+}
+
+int hbam_gpu_set_locate(hbam_gpu* g, uint64_t seg_bytes, uint32_t cap_limit) {
+  if (!g->f) {
+    g->err = "hbam_gpu_set_locate needs a loaded file";
+    return HBAM_E_STATE;
+  }
+  set_locate(*g->f, seg_bytes, cap_limit);
+  return HBAM_OK;
+}
+
+int hbam_gpu_locate_counters(hbam_gpu* g, uint64_t out[2]) {
+  out[0] = out[1] = 0;
+  if (!g->f) return HBAM_E_STATE;
+  out[0] = g->f->pipe().locate_anchored();
+  out[1] = g->f->pipe().locate_declined();
   return HBAM_OK;
 }
 

@@ -190,6 +190,197 @@ __global__ __launch_bounds__(256) void k_bgzf_scan(const uint8_t* __restrict__ b
     if (s_base + t < cap) cand[s_base + t] = s_cand[t];
 }
 
+// ---------------------------------------------------------------------------
+// Anchored locate: the block table of a range whose start is a known block
+// start, from a fraction of its bytes.  The range is cut into segments of
+// seg bytes; segment j = [lo + j * seg, min(lo + (j + 1) * seg, hi)).
+//   k_bgzf_anchor_walk  one wave per segment: the segment's anchor (the first
+//        header match whose successor matches too; lo for segment 0), then
+//        the BSIZE walk from it up to the segment's end: block count and exit
+//   k_bgzf_link         one workgroup: every walk's exit is the next
+//        non-empty segment's anchor and the last exit reaches hi; the
+//        exclusive scan of the counts
+//   k_bgzf_seg_emit     one lane per segment: the walk again (its loads hit
+//        L2), writing the block starts in file order
+// Any doubt (a walk step that is no header, a broken link, a range not walked
+// to hi) sets res[0]; the caller then runs the scan path.  Every loop is
+// bounded: a search covers one segment, a walk step advances >= 26 bytes.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kNoAnchor = ~0ull;
+#ifndef HBAM_ANCHOR_U
+#define HBAM_ANCHOR_U 4  // wave steps (1 KiB each) per search iteration
+#endif
+
+// the scan's header test at p (p + 18 <= the readable range) plus a BSIZE
+// that holds a block: no weaker than k_bgzf_walk's framing rules
+__device__ __forceinline__ bool bgzf_header_at(const uint8_t* __restrict__ file, uint64_t p, uint32_t* total) {
+  const uint32_t w0 = ldu32(file, p);
+  const uint32_t xlen = ldu32(file, p + 10) & 0xffffu;
+  const uint32_t sub = ldu32(file, p + 12);
+  *total = (ldu32(file, p + 16) & 0xffffu) + 1;
+  return w0 == 0x04088b1fu && xlen == 6 && sub == 0x00024342u && *total >= 26;
+}
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t l2 = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
+    const uint32_t h2 = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
+    const uint64_t v2 = ((uint64_t)h2 << 32) | l2;
+    v = v2 < v ? v2 : v;
+  }
+  return v;
+}
+
+// file: absolute file coordinates, 16 B aligned at offset 0 (as the scan).
+// res[0] |= 1: declined.
+__global__ __launch_bounds__(256) void k_bgzf_anchor_walk(const uint8_t* __restrict__ file, uint64_t lo, uint64_t hi,
+                                                          uint64_t seg, uint32_t nseg, uint32_t partial,
+                                                          uint64_t* __restrict__ anchor, uint64_t* __restrict__ exitp,
+                                                          uint32_t* __restrict__ cnt, uint32_t* __restrict__ res) {
+  const uint32_t j = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;  // wave-uniform
+  if (j >= nseg) return;
+  const uint32_t lane = lane_id();
+  const uint64_t s0 = lo + (uint64_t)j * seg;
+  const uint64_t end = s0 + seg < hi ? s0 + seg : hi;
+  uint64_t a = j == 0 ? lo : kNoAnchor;
+  if (j != 0) {
+    // The scan's wave step: lane i reads 16 B chunk c0 + i (one coalesced
+    // 1 KiB load), four steps per iteration, the next iteration's loads in
+    // flight while this one's chunks are tested.  The first iteration with
+    // an anchor holds the segment's first one: iterations are in file order.
+    constexpr int kU = HBAM_ANCHOR_U;
+    const uint4* chunks = reinterpret_cast<const uint4*>(file);
+    const uint64_t cend = (end + 15) / 16;
+    auto fetch = [&](uint64_t c0, uint4* vv, uint32_t& tail) {
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const uint64_t c = c0 + 64 * u + lane;
+        vv[u] = c < cend ? chunks[c] : make_uint4(0, 0, 0, 0);
+      }
+      const uint64_t clast = c0 + 64 * (kU - 1) + 63;  // (the file is padded past hi)
+      tail = lane == 63 && clast < cend ? *reinterpret_cast<const uint32_t*>(file + 16 * clast + 16) : 0u;
+    };
+    uint4 nv[kU];
+    uint32_t ntail = 0;
+    const uint64_t cfirst = s0 / 16;
+    fetch(cfirst, nv, ntail);
+    for (uint64_t c0 = cfirst; c0 < cend && a == kNoAnchor; c0 += 64 * kU) {
+      uint4 vv[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) vv[u] = nv[u];
+      const uint32_t tail = ntail;
+      if (c0 + 64 * kU < cend) fetch(c0 + 64 * kU, nv, ntail);
+      uint64_t best = kNoAnchor;
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const uint64_t c = c0 + 64 * u + lane;
+        const uint4 v = vv[u];
+        uint32_t nx = (uint32_t)__shfl_down((int)v.x, 1, 64);
+        const uint32_t next0 = u + 1 < kU ? (uint32_t)__shfl((int)vv[u + 1 < kU ? u + 1 : u].x, 0, 64) : 0u;
+        if (lane == 63) nx = u + 1 < kU ? next0 : tail;
+        const uint32_t w[5] = {v.x, v.y, v.z, v.w, nx};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t x = w[k] ^ 0x1f1f1f1fu;
+          uint32_t hz = (x - 0x01010101u) & ~x & 0x80808080u;  // a byte of w[k] may be 0x1f (superset)
+          while (hz) {
+            const uint32_t byte = (uint32_t)__builtin_ctz(hz) >> 3;
+            hz &= hz - 1;
+            if (__builtin_amdgcn_alignbyte(w[k + 1], w[k], byte) != 0x04088b1fu) continue;
+            const uint64_t p = 16 * c + 4 * k + byte;
+            if (p < s0 || p >= end || p + 18 > hi || p >= best) continue;
+            uint32_t total, t2;
+            if (!bgzf_header_at(file, p, &total)) continue;
+            const uint64_t q = p + total;  // the successor: a header too, or past the range
+            if (q < hi && (q + 18 > hi || !bgzf_header_at(file, q, &t2))) continue;
+            best = p;
+          }
+        }
+      }
+      if (__any(best != kNoAnchor)) a = wave_min_u64(best);
+    }
+  }
+  if (lane != 0) return;
+  // the BSIZE walk from the anchor to the segment's end.  The last block of
+  // the range may be cut by hi: it is counted (k_bgzf_verify's partial rule
+  // sees it) and ends the walk.
+  uint64_t p = a;
+  uint32_t n = 0;
+  if (a != kNoAnchor) {
+    while (p < end) {
+      uint32_t total;
+      if (p + 18 > hi || !bgzf_header_at(file, p, &total)) {
+        atomicOr(&res[0], 1u);
+        break;
+      }
+      ++n;
+      p += total;
+      if (p > hi) {
+        if (!partial) atomicOr(&res[0], 1u);
+        break;
+      }
+    }
+  }
+  anchor[j] = a;
+  exitp[j] = a != kNoAnchor ? p : kNoAnchor;
+  cnt[j] = n;
+}
+
+// One workgroup over all segments, thread t on a contiguous run of them.
+// res[0] |= 1 on a broken link or a range not walked to hi, res[1] = the
+// blocks of the range (saturated), offs[j] = the blocks before segment j.
+constexpr int kLinkThreads = 1024;
+struct LastExitOp {
+  __device__ __forceinline__ uint64_t operator()(uint64_t x, uint64_t y) const { return y != kNoAnchor ? y : x; }
+};
+__global__ __launch_bounds__(kLinkThreads) void k_bgzf_link(const uint64_t* __restrict__ anchor,
+                                                            const uint64_t* __restrict__ exitp,
+                                                            const uint32_t* __restrict__ cnt, uint32_t nseg,
+                                                            uint64_t hi, uint32_t* __restrict__ offs,
+                                                            uint32_t* __restrict__ res) {
+  using ScanSum = hipcub::BlockScan<uint64_t, kLinkThreads>;
+  __shared__ typename ScanSum::TempStorage tmp;
+  const uint32_t per = (nseg + kLinkThreads - 1) / kLinkThreads;
+  const uint32_t j0 = min(threadIdx.x * per, nseg), j1 = min(j0 + per, nseg);
+  uint64_t sum = 0, last = kNoAnchor;
+  for (uint32_t j = j0; j < j1; ++j) {
+    sum += cnt[j];
+    if (anchor[j] != kNoAnchor) last = exitp[j];
+  }
+  uint64_t before = 0, prev = kNoAnchor, total = 0;
+  ScanSum(tmp).ExclusiveSum(sum, before, total);
+  __syncthreads();
+  ScanSum(tmp).ExclusiveScan(last, prev, kNoAnchor, LastExitOp());
+  bool bad = false;
+  for (uint32_t j = j0; j < j1; ++j) {
+    offs[j] = before < 0xffffffffull ? (uint32_t)before : 0xffffffffu;
+    before += cnt[j];
+    const uint64_t a = anchor[j];
+    if (a == kNoAnchor) continue;
+    if (prev != kNoAnchor && prev != a) bad = true;  // (segment 0's anchor is lo itself)
+    prev = exitp[j];
+  }
+  // the chain's last exit: hi, or past it (a cut block, which the walk judged)
+  if (threadIdx.x == kLinkThreads - 1 && (prev == kNoAnchor || prev < hi)) bad = true;
+  if (bad) atomicOr(&res[0], 1u);
+  if (threadIdx.x == 0) res[1] = total < 0xffffffffull ? (uint32_t)total : 0xffffffffu;
+}
+
+// The block starts of every segment at its offset: the checked walk again.
+__global__ void k_bgzf_seg_emit(const uint8_t* __restrict__ file, const uint64_t* __restrict__ anchor,
+                                const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ offs, uint32_t nseg,
+                                uint32_t cap, uint64_t* __restrict__ out) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nseg) return;
+  uint64_t p = anchor[j];
+  const uint32_t n = cnt[j], o = offs[j];
+  for (uint32_t i = 0; i < n && o + i < cap; ++i) {
+    out[o + i] = p;
+    p += (ldu32(file, p + 16) & 0xffffu) + 1;
+  }
+}
+
 // Verify the sorted candidate chain and fill BlockInfo.  flags[0] |= 1 on any
 // break (fallback), flags[1] = first block index with ISIZE > 64 KiB,
 // flags[3] += the empty blocks (ISIZE 0: candidates for dead positions).
@@ -4393,6 +4584,19 @@ hipError_t launch_bgzf_scan(const uint8_t* file, uint64_t buf_base, uint64_t lo,
   const uint64_t nc = (hi - a + 15) / 16;  // 16 B per lane and step, 4 steps per iteration
   hipLaunchKernelGGL(k_bgzf_scan, dim3(grid_for((nc + 3) / 4, 256, HBAM_SCAN_GRID)), dim3(256), 0, s, file + a, hi - a, a, lo,
                      cand, cap, count);
+  return hipGetLastError();
+}
+hipError_t launch_bgzf_anchor_walk(const uint8_t* file, uint64_t lo, uint64_t hi, uint64_t seg, uint32_t nseg,
+                                   uint32_t partial, uint64_t* anchor, uint64_t* exitp, uint32_t* cnt, uint32_t* offs,
+                                   uint32_t* res, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_anchor_walk, dim3((nseg + 3) / 4), dim3(256), 0, s, file, lo, hi, seg, nseg, partial,
+                     anchor, exitp, cnt, res);
+  hipLaunchKernelGGL(k_bgzf_link, dim3(1), dim3(kLinkThreads), 0, s, anchor, exitp, cnt, nseg, hi, offs, res);
+  return hipGetLastError();
+}
+hipError_t launch_bgzf_seg_emit(const uint8_t* file, const uint64_t* anchor, const uint32_t* cnt,
+                                const uint32_t* offs, uint32_t nseg, uint32_t n, uint64_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_bgzf_seg_emit, dim3((nseg + 63) / 64), dim3(64), 0, s, file, anchor, cnt, offs, nseg, n, out);
   return hipGetLastError();
 }
 hipError_t launch_bgzf_verify(const uint8_t* file, uint64_t lo, uint64_t hi, const uint64_t* cand, uint32_t n,

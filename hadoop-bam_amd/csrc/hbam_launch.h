@@ -68,6 +68,15 @@ hipError_t launch_bgzf_verify(const uint8_t* file, uint64_t lo, uint64_t hi, con
                               BlockInfo* blocks, uint32_t* flags, uint32_t partial, hipStream_t s);
 hipError_t launch_bgzf_walk(const uint8_t* file, uint64_t lo, uint64_t hi, BlockInfo* blocks, uint32_t cap,
                             uint32_t* out, uint32_t partial, hipStream_t s);
+// Anchored locate of [lo, hi), lo a block start, in nseg segments of seg bytes
+// (per-segment scratch: anchor, exitp, cnt, offs).  res[0] != 0: declined (run
+// the scan path); else res[1] = the blocks of the range, and
+// launch_bgzf_seg_emit writes their n starts to out in file order.
+hipError_t launch_bgzf_anchor_walk(const uint8_t* file, uint64_t lo, uint64_t hi, uint64_t seg, uint32_t nseg,
+                                   uint32_t partial, uint64_t* anchor, uint64_t* exitp, uint32_t* cnt, uint32_t* offs,
+                                   uint32_t* res, hipStream_t s);
+hipError_t launch_bgzf_seg_emit(const uint8_t* file, const uint64_t* anchor, const uint32_t* cnt,
+                                const uint32_t* offs, uint32_t nseg, uint32_t n, uint64_t* out, hipStream_t s);
 // ustart = base + exclusive scan of ISIZE
 hipError_t launch_block_ustart(BlockInfo* blocks, uint32_t n, uint64_t* tmp_isize, uint64_t* tmp_ustart,
                                void* scan_tmp, size_t* scan_bytes, uint64_t base, hipStream_t s);

@@ -67,7 +67,8 @@ Pipeline::Pipeline(int device) : device_(device) {
       tinfo_[0], tinfo_[1], flist_[0], flist_[1], pstats_, g_, x_, x2_, entry_, base_arr_, summary_, dead_, cand_, sorted_, isz_, ust_, cnt_, flags_,
       errv_, need_, rec_pos_, rec_voff_, rcand_, force_, wcnt_, counters_, list_, scan_tmp_, cols_, long_rec_,
       long_n_, wbuf_, woffs_, wbad_, scalars_, fuse_, sort_word_, sort_word2_, sort_slen_, sort_doff_, sort_len_,
-      sort_iota_, sort_perm_, sort_tmp_);
+      sort_iota_, sort_perm_, sort_tmp_, seg_anchor_, seg_exit_, seg_cnt_, seg_off_);
+  if (const char* e = getenv("HBAM_LOCATE_SEG")) locate_seg_ = strtoull(e, nullptr, 0);
   for (auto& e : ev_) (void)hipEventCreate(&e);
   for (auto& e : sync_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& e : tab_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
@@ -402,20 +403,50 @@ int Pipeline::locate_range(uint64_t lo, uint64_t hi, bool partial, bool free_sta
   const uint64_t len = hi - lo;
   // candidate capacity assumes >= 1 KiB per block on average; denser files
   // (or any chain break) take the serial walk, whose table bound is len/26.
-  const uint32_t cap = (uint32_t)std::min<uint64_t>(len / 1024 + 4096, 0x7fffffffu);
+  uint32_t cap = (uint32_t)std::min<uint64_t>(len / 1024 + 4096, 0x7fffffffu);
+  if (locate_cap_limit_) cap = std::min(cap, locate_cap_limit_);
   const uint32_t walk_cap = (uint32_t)std::min<uint64_t>(len / 26 + 16, 0x7fffffffu);
   HIPCHK(cand_.reserve(cap));
-  HIPCHK(flags_.reserve(5));
+  HIPCHK(flags_.reserve(8));
   // {0, 0, 0xffffffff, 0, 0} by fill kernels: a small pageable H2D can wait
   // behind other contexts' or the drop-in batches' copies on the DMA engines
-  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p), 0, 5, s));
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p), 0, 7, s));
   HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 2), -1, 1, s));
   // flags_[0] = candidate count, [1] = chain break, [2] = first big ISIZE, [3] = cut tail,
-  // [4] = empty blocks
-  HIPCHK(launch_bgzf_scan(fbase, base_, lo, hi, cand_.p, cap, flags_.p, s));
+  // [4] = empty blocks, [5] = anchored locate declined, [6] = its block count
   uint32_t count = 0;
-  HIPCHK(rb(&count, flags_.p, 4, s));
-  HIPCHK(rb_sync(s));
+  // Anchored locate: lo is a block start, so the table is the BSIZE chain
+  // from lo.  Walks from one anchor per segment find it from the bytes around
+  // the segment boundaries and the headers; the block starts land in sorted_
+  // in file order, as the scan and the sort leave them.  Whenever the walks
+  // cannot vouch for the whole chain they decline, and the scan path below
+  // locates the range as if they had not run (its errors are the range's).
+  bool anchored = false;
+  if (!free_start && locate_seg_ && len > 0 && (len + locate_seg_ - 1) / locate_seg_ <= 0x7fffffffu) {
+    const uint32_t nseg = (uint32_t)((len + locate_seg_ - 1) / locate_seg_);
+    HIPCHK(seg_anchor_.reserve(nseg));
+    HIPCHK(seg_exit_.reserve(nseg));
+    HIPCHK(seg_cnt_.reserve(nseg));
+    HIPCHK(seg_off_.reserve(nseg));
+    HIPCHK(launch_bgzf_anchor_walk(fbase, lo, hi, locate_seg_, nseg, partial ? 1u : 0u, seg_anchor_.p, seg_exit_.p,
+                                   seg_cnt_.p, seg_off_.p, flags_.p + 5, s));
+    uint32_t res[2] = {1, 0};
+    HIPCHK(rb(res, flags_.p + 5, 8, s));
+    HIPCHK(rb_sync(s));
+    if (!res[0] && res[1] > 0 && res[1] <= cap) {
+      count = res[1];
+      HIPCHK(sorted_.reserve(count));
+      HIPCHK(launch_bgzf_seg_emit(fbase, seg_anchor_.p, seg_cnt_.p, seg_off_.p, nseg, count, sorted_.p, s));
+      anchored = true;
+    } else {
+      ++locate_declined_;
+    }
+  }
+  if (!anchored) {
+    HIPCHK(launch_bgzf_scan(fbase, base_, lo, hi, cand_.p, cap, flags_.p, s));
+    HIPCHK(rb(&count, flags_.p, 4, s));
+    HIPCHK(rb_sync(s));
+  }
   bool serial = count > cap || (count == 0 && len > 0);
   if (free_start && count == 0) return kOk;  // no header in the window: no blocks
   uint32_t n = serial ? 0 : count;
@@ -436,11 +467,13 @@ int Pipeline::locate_range(uint64_t lo, uint64_t hi, bool partial, bool free_sta
   std::vector<uint64_t> starts;  // free start: candidates to try, in order
   if (!serial && n > 0) {
     HIPCHK(dblocks_.grow(nprev + n + 1));
-    HIPCHK(sorted_.reserve(n));
-    size_t tmp_bytes = 0;
-    HIPCHK(sort_u64(nullptr, &tmp_bytes, cand_.p, sorted_.p, n, s));
-    HIPCHK(scan_tmp_.reserve(tmp_bytes + 16));
-    HIPCHK(sort_u64(scan_tmp_.p, &tmp_bytes, cand_.p, sorted_.p, n, s));
+    if (!anchored) {
+      HIPCHK(sorted_.reserve(n));
+      size_t tmp_bytes = 0;
+      HIPCHK(sort_u64(nullptr, &tmp_bytes, cand_.p, sorted_.p, n, s));
+      HIPCHK(scan_tmp_.reserve(tmp_bytes + 16));
+      HIPCHK(sort_u64(scan_tmp_.p, &tmp_bytes, cand_.p, sorted_.p, n, s));
+    }
     if (free_start) {
       starts.resize(std::min<uint32_t>(n, kMaxFreeStarts));
       HIPCHK(rb(starts.data(), sorted_.p, starts.size() * 8, s));
@@ -459,6 +492,7 @@ int Pipeline::locate_range(uint64_t lo, uint64_t hi, bool partial, bool free_sta
     if (int rc = queue_table(n)) return rc;
     HIPCHK(rb_sync(s));
     if (!fl[0] && empty_blocks_ != kEmptyUnknown) empty_blocks_ += fl[3];
+    if (anchored) ++(fl[0] ? locate_declined_ : locate_anchored_);  // (the walks checked what verify checks)
     if (fl[0]) serial = true;
     else if (fl[1] != 0xffffffffu) return fail(kErrFormat, "BGZF block with ISIZE > 65536 (unsupported on device)");
     else if (fl[2]) {  // the last candidate's block is cut by hi: next range

@@ -179,6 +179,12 @@ hipError_t create_stream(hipStream_t* s, StreamLevel level);
 // hadoopbam.samheaderreader.validation-stringency property).
 enum Stringency : int { kStrict = 0, kLenient = 1, kSilent = 2 };
 
+// Anchored locate: bytes per segment (the S sweep)
+#ifndef HBAM_LOCATE_SEG_BYTES
+#define HBAM_LOCATE_SEG_BYTES (512u << 10)
+#endif
+constexpr uint64_t kLocateSegBytes = HBAM_LOCATE_SEG_BYTES;
+
 class Pipeline {
  public:
   explicit Pipeline(int device);
@@ -318,6 +324,18 @@ class Pipeline {
   uint64_t record_fallbacks() const { return record_fallbacks_; }
   uint64_t records_after_stop() const { return records_after_stop_; }
   uint64_t inflate_launches() const { return inflate_launches_; }
+  // Anchored locate (locate_range): ranges whose table it produced / ranges
+  // it declined, which the scan path then located
+  uint64_t locate_anchored() const { return locate_anchored_; }
+  uint64_t locate_declined() const { return locate_declined_; }
+  // Segment bytes of the anchored locate (0: the scan path only; default
+  // kLocateSegBytes, or HBAM_LOCATE_SEG from the environment) and a bound on
+  // the candidate capacity (0: none).  Test and measurement hooks.
+  void set_locate(uint64_t seg_bytes, uint32_t cap_limit) {
+    locate_seg_ = seg_bytes;
+    locate_cap_limit_ = cap_limit;
+  }
+  uint64_t locate_seg() const { return locate_seg_; }
   // LZ77 tokens phase A wrote for the window's blocks in its last inflate
   // (the sum of HuffOut::ntok; a synchronous read, for measurements)
   int inflate_tokens(uint64_t* n);
@@ -407,6 +425,9 @@ class Pipeline {
   uint32_t after_stop_flag_ = 0;     // (read back with a span's last readback)
   bool after_stop_pending_ = false;
   uint64_t inflate_launches_ = 0;  // phase A/B launch pairs so far
+  uint64_t locate_anchored_ = 0, locate_declined_ = 0;
+  uint64_t locate_seg_ = kLocateSegBytes;
+  uint32_t locate_cap_limit_ = 0;
 
   DevBuf<uint8_t> du_;
   std::vector<uint8_t> inflated_;  // per block flag
@@ -426,6 +447,8 @@ class Pipeline {
   DevBuf<uint64_t> g_, x_, x2_, entry_, base_arr_, summary_, dead_;
   DevBuf<uint64_t> cand_, sorted_, isz_, ust_;  // locate scratch
   DevBuf<uint32_t> cnt_, flags_;
+  DevBuf<uint64_t> seg_anchor_, seg_exit_;  // anchored locate: per segment
+  DevBuf<uint32_t> seg_cnt_, seg_off_;
   DevBuf<int32_t> errv_;
   DevBuf<unsigned long long> need_;
   DevBuf<uint64_t> rec_pos_, rec_voff_;

@@ -97,6 +97,10 @@ _sig("hbam_query_intervals", C.c_int, [P, P, u64, P, u64])
 _sig("hbam_query_unmapped", C.c_int, [P, u64])
 _sig("hbam_query_next", C.c_int, [P, u64, C.POINTER(Batch)])
 _sig("hbam_pipeline_counters", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_locate_counters", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_set_locate", C.c_int, [P, u64, u32])
+_sig("hbam_gpu_set_locate", C.c_int, [P, u64, u32])
+_sig("hbam_gpu_locate_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_token_count", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_path_counts", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_narrow_counts", C.c_int, [P, C.POINTER(u64)])
@@ -147,6 +151,7 @@ _sig("hbam_bai_summarize", C.c_int, [P, u64, C.POINTER(BaiSummary)])
 _sig("hbam_bai_query", C.c_int, [P, u64, P, u64, C.POINTER(P), C.POINTER(u64)])
 
 BGZF_EOF = 1
+LOCATE_SEG_DEFAULT = (1 << 64) - 1  # hbam_set_locate: the built-in segment size
 SORT_KEY, SORT_COORDINATE = 0, 1  # hbam_sort_writables orders
 SORT_ORDERS = {"key": SORT_KEY, "coordinate": SORT_COORDINATE}
 BAI_METADATA = 1  # hbam_build_bai: the pseudo-bins 37450 and the trailing n_no_coor
@@ -481,9 +486,20 @@ class BamFile:
         rc = _L.hbam_pipeline_counters(self._h, v)
         if rc != OK:
             raise self._err(rc)
+        w = (u64 * 2)()
+        rc = _L.hbam_locate_counters(self._h, w)
+        if rc != OK:
+            raise self._err(rc)
         return dict(zip(("link_fallbacks", "link_rewalks", "record_fallbacks", "inflate_launches",
-                         "records_after_stop"),
-                        (int(x) for x in v)))
+                         "records_after_stop", "locate_anchored", "locate_declined"),
+                        (int(x) for x in list(v) + list(w))))
+
+    def set_locate(self, seg_bytes=LOCATE_SEG_DEFAULT, cap_limit=0):
+        """hbam_set_locate: the anchored locate's segment bytes (0: the full
+        scan only) and a bound on a range's candidate capacity (0: none)."""
+        rc = _L.hbam_set_locate(self._h, seg_bytes, cap_limit)
+        if rc != OK:
+            raise self._err(rc)
 
     def inflate_token_count(self):
         """LZ77 tokens phase A wrote in the last pass over the current window
@@ -888,6 +904,20 @@ class Gpu:
         rc = _L.hbam_gpu_set_stringency(self._h, stringency)
         if rc != OK:
             raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+
+    def set_locate(self, seg_bytes=LOCATE_SEG_DEFAULT, cap_limit=0):
+        """hbam_gpu_set_locate (see BamFile.set_locate); needs a loaded file."""
+        rc = _L.hbam_gpu_set_locate(self._h, seg_bytes, cap_limit)
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+
+    def locate_counters(self):
+        """(locate_anchored, locate_declined) of the loaded file's pipeline."""
+        w = (u64 * 2)()
+        rc = _L.hbam_gpu_locate_counters(self._h, w)
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        return int(w[0]), int(w[1])
 
     def run(self, timing=False, decode=True, digest=False):
         st = GpuStats()

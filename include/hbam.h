@@ -451,6 +451,23 @@ int hbam_decode_span_device(hbam_ctx *ctx, uint64_t vstart, uint64_t vend, int32
  * assert which path a decode took. */
 int hbam_pipeline_counters(hbam_ctx *ctx, uint64_t out[5]);
 
+/* The BGZF block table of a range that starts at a known block start is
+ * located by anchored chain walks: the range is cut into segments, one true
+ * block start is found near every segment boundary, BSIZE is walked from
+ * there, and the walks must join.  When they cannot vouch for the whole chain
+ * they decline and the full header scan locates the range, so results and
+ * errors never depend on which path ran.  Cumulative since the open, counted
+ * on the host: out[0] ranges the walks located, out[1] ranges they declined.
+ * (Kept apart from hbam_pipeline_counters, whose callers pass five words.) */
+int hbam_locate_counters(hbam_ctx *ctx, uint64_t out[2]);
+/* Test and measurement hook: the segment size of the anchored walks in bytes
+ * (0: the full scan only; HBAM_LOCATE_SEG_DEFAULT: the built-in size, which
+ * HBAM_LOCATE_SEG in the environment overrides at open) and an upper bound on
+ * the candidate capacity of a range (0: none; ranges with more blocks take
+ * the serial walk).  The window in place is located again at its next use. */
+#define HBAM_LOCATE_SEG_DEFAULT UINT64_MAX
+int hbam_set_locate(hbam_ctx *ctx, uint64_t seg_bytes, uint32_t cap_limit);
+
 /* The LZ77 tokens inflate phase A wrote for the blocks of the ctx's current
  * window in its last pass (u32 each: phase A's output bytes / 4).  A
  * measurement helper for the bench's traffic figures (no reference
@@ -516,6 +533,9 @@ int hbam_gpu_set_window(hbam_gpu *g, uint64_t window_bytes);
 /* Validation stringency of the files loaded from now on (HBAM_STRICT when
  * never set); an unknown value -> HBAM_E_ARG. */
 int hbam_gpu_set_stringency(hbam_gpu *g, int32_t stringency);
+/* hbam_set_locate / hbam_locate_counters of the loaded file's pipeline */
+int hbam_gpu_set_locate(hbam_gpu *g, uint64_t seg_bytes, uint32_t cap_limit);
+int hbam_gpu_locate_counters(hbam_gpu *g, uint64_t out[2]);
 /* One pass of the hot path over the resident file, first record to EOF:
  * BGZF discovery, inflate, record scan, field decode + keys + voffs, window by
  * window (flags as hbam_decode_span_device). */
