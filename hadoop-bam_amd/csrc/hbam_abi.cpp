@@ -17,6 +17,7 @@
 #include "hbam_mem.h"
 #include "hbam_host.h"
 #include "hbam_launch.h"
+#include "hbam_merge.h"
 
 using hadoop_bam::BAMInputFormat;
 using hadoop_bam::BamFile;
@@ -42,6 +43,8 @@ struct hbam_ctx {
   bool last_is_writables = false;
   std::unique_ptr<QueryCursor> query;  // the open bounded traversal (hbam_query_*), if any
   bool last_is_query = false;          // the last batch came from hbam_query_next
+  std::unique_ptr<hbam::Merger> merge;  // the open merge (hbam_merge_*), if any (destroyed first: its buffers
+                                        // wait for the pipeline's streams)
 };
 
 // Forget the split and the query being read: the call about to run moves the
@@ -685,6 +688,85 @@ int hbam_decode_writables(hbam_ctx* ctx, const void* buf, uint64_t len, const ui
   if (span.status != HBAM_OK) {
     ctx->err = span.error;
     return span.status;
+  }
+  return HBAM_OK;
+}
+
+int hbam_merge_begin(hbam_ctx* ctx, int32_t order) {
+  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (ctx->merge) {
+    ctx->err = "hbam_merge_begin: a merge is already open on this ctx (hbam_merge_end closes it)";
+    return HBAM_E_STATE;
+  }
+  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE) {
+    ctx->err = "unknown sort order " + std::to_string(order);
+    return HBAM_E_ARG;
+  }
+  hbam::Pipeline& p = ctx->f ? ctx->f->pipe() : *ctx->codec;
+  ctx->merge.reset(new hbam::Merger(p, order));
+  return HBAM_OK;
+}
+
+int hbam_merge_add_run(hbam_ctx* ctx, const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n,
+                       const uint64_t* words) {
+  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!ctx->merge || ctx->merge->planned()) {
+    ctx->err = ctx->merge ? "hbam_merge_add_run after hbam_merge_plan" : "hbam_merge_add_run needs hbam_merge_begin";
+    return HBAM_E_STATE;
+  }
+  hbam::Merger& m = *ctx->merge;
+  int rc = m.begin_run(buf, len, offs, n);
+  if (rc != HBAM_OK) {
+    ctx->err = "hbam_merge_add_run: " + m.error();
+    return rc;
+  }
+  if (!words && n) {
+    // the reducer's case: readFields of the run's values, the words from its columns
+    hbam_batch b;
+    rc = hbam_decode_writables(ctx, buf, len, offs, n, &b);
+    if (rc != HBAM_OK) return rc;
+  }
+  rc = m.finish_run(words, words ? nullptr : &ctx->wspan.col);
+  if (rc != HBAM_OK) ctx->err = "hbam_merge_add_run: " + m.error();
+  return rc;
+}
+
+int hbam_merge_plan(hbam_ctx* ctx, uint64_t part_bytes, uint64_t* n_parts, uint64_t* n_records, uint64_t* bytes) {
+  *n_parts = *n_records = *bytes = 0;
+  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!ctx->merge || ctx->merge->planned()) {
+    ctx->err = ctx->merge ? "hbam_merge_plan was already called" : "hbam_merge_plan needs hbam_merge_begin";
+    return HBAM_E_STATE;
+  }
+  const int rc = ctx->merge->plan(part_bytes ? part_bytes : (1ull << 30), n_parts, n_records, bytes);
+  if (rc != HBAM_OK) ctx->err = "hbam_merge_plan: " + ctx->merge->error();
+  return rc;
+}
+
+int hbam_merge_next(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, uint64_t* src, uint64_t* n,
+                    uint64_t* len) {
+  *n = *len = 0;
+  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!ctx->merge || !ctx->merge->planned()) {
+    ctx->err = "hbam_merge_next needs hbam_merge_plan";
+    return HBAM_E_STATE;
+  }
+  const int rc = ctx->merge->next(out, cap, offs, src, n, len);
+  if (rc != HBAM_OK) ctx->err = "hbam_merge_next: " + ctx->merge->error();
+  return rc;
+}
+
+int hbam_merge_end(hbam_ctx* ctx) {
+  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  ctx->merge.reset();
+  return HBAM_OK;
+}
+
+int hbam_merge_times(hbam_ctx* ctx, float plan_ms[3], float part_ms[3]) {
+  if (!ctx || !ctx->merge) return HBAM_E_STATE;
+  for (int i = 0; i < 3; ++i) {
+    plan_ms[i] = ctx->merge->plan_ms[i];
+    part_ms[i] = ctx->merge->part_ms[i];
   }
   return HBAM_OK;
 }

@@ -182,6 +182,48 @@ hipError_t launch_sort_offsets(void* tmp, size_t tmp_bytes, const uint32_t* len,
 // readable 16 bytes past its last record
 hipError_t launch_sort_gather(const uint8_t* u, const uint64_t* rec_pos, const int32_t* ref_id, const uint32_t* perm,
                               const uint64_t* doff, uint64_t n, uint64_t total, uint8_t* dst, hipStream_t s);
+// k_sort_words alone: the sort words, encoded lengths and iota of n decoded records
+hipError_t launch_sort_words(const Columns& col, uint64_t n, int order, uint64_t* word, uint32_t* len, uint32_t* iota,
+                             hipStream_t s);
+// Merge of k sorted runs of SAMRecordWritable encodings (hbam_merge.hip), total
+// records n < 2^31 - 1.  A record's global index is run-major: run_base[r] + i
+// (run_base: k + 1 u64).  Every run's n_r + 1 offsets lie back to back in one
+// array, run r's at run_base[r] + r.
+constexpr uint64_t kMergeMinRecord = 36;  // block_size + the fixed fields
+// temporary storage of the radix sort of n pairs and of the scans over n + 1 entries
+hipError_t merge_tmp_bytes(uint64_t n, size_t* bytes);
+// one run: rlen[i] = offs[i + 1] - offs[i]; bad[0] = the first record whose
+// framing is not an increasing pair >= kMergeMinRecord apart inside len,
+// bad[1] = the first record whose word is below its predecessor's (word ==
+// nullptr: not checked); both preset to ~0 by the caller
+hipError_t launch_merge_check(const uint64_t* offs, uint64_t n, uint64_t len, const uint64_t* word, uint32_t* rlen,
+                              unsigned long long* bad, hipStream_t s);
+// perm[j] = the global index of the j-th output record (stable; idx: n u32 of scratch)
+hipError_t launch_merge_perm(void* tmp, size_t tmp_bytes, const uint64_t* word, uint64_t* word_sorted, uint32_t* idx,
+                             uint32_t* perm, uint64_t n, hipStream_t s);
+// flag[j] = output record j starts a part (doff[j] / part_bytes differs from
+// its predecessor's), num = the exclusive sum of flag over n + 1 entries: num[n] = the parts
+hipError_t launch_merge_heads(void* tmp, size_t tmp_bytes, const uint64_t* doff, uint64_t n, uint64_t part_bytes,
+                              uint32_t* flag, uint32_t* num, hipStream_t s);
+// part_first / part_start (parts + 1 entries: the first record / output byte of
+// each part, the last = n / doff[n]), rank (n u32: the inverse of perm) and
+// cut[p * k + r], p <= parts: the records of run r before part p; cut_off = the
+// offset in run r at which they end (off: the runs' offsets as described above)
+hipError_t launch_merge_cuts(const uint32_t* flag, const uint32_t* num, const uint64_t* doff, const uint32_t* perm,
+                             uint64_t n, const uint64_t* run_base, uint32_t k, uint64_t parts, uint32_t* part_first,
+                             uint64_t* part_start, uint32_t* rank, const uint64_t* off, uint32_t* cut,
+                             uint64_t* cut_off, hipStream_t s);
+// one part of n records (perm, doff: its first entries; dbase = doff[0]):
+// src_pos[j] = slice_base[run] + the record's offset in its run, src_id[j] =
+// run << 32 | record, part_offs[j] = doff[j] - dbase (n + 1 entries)
+hipError_t launch_merge_src(const uint32_t* perm, const uint64_t* doff, uint64_t n, uint64_t dbase,
+                            const uint64_t* run_base, uint32_t k, const uint64_t* off, const uint64_t* slice_base,
+                            uint64_t* src_pos, uint64_t* src_id, uint64_t* part_offs, hipStream_t s);
+// dst[doff[j] - dbase, doff[j + 1] - dbase) = the bytes at u + src_pos[j]
+// (k_sort_gather without perm and bin patch); total = doff[n] - dbase; dst holds
+// total rounded up to 16, u is readable 16 bytes past its last record
+hipError_t launch_merge_gather(const uint8_t* u, const uint64_t* src_pos, const uint64_t* doff, uint64_t n,
+                               uint64_t dbase, uint64_t total, uint8_t* dst, hipStream_t s);
 // SAMRecordWritable.readFields of n framed values; *bad = min((i << 8) | status)
 hipError_t launch_wr_decode(const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n, const Columns& col,
                             uint64_t* rec_pos, unsigned long long* bad, hipStream_t s);

@@ -11,6 +11,8 @@
 //        starts, doff[n] = the output's bytes
 //   k_sort_gather the record bytes, divided by output bytes: a workgroup owns
 //        one 32 KiB output tile, whatever the records' lengths
+//        (k_sort_gather<true>: the same gather for one part of a merge of
+//        sorted runs, hbam_merge.hip, from a per-record source table)
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stddef.h>
@@ -84,12 +86,18 @@ constexpr uint32_t kSortTable = 1024;
 constexpr uint64_t kSortUnplaced = 1ull << 63;
 static_assert(kSortTile / 36 + 2 < kSortTable, "every record of a tile and the next one's start fit the table");
 
+// kMerge (one part of hbam_merge_next): rec_pos[j] is the j-th output record's
+// own source position (k_merge_src's table: no perm), the encodings already
+// carry indexBin = 0 (no ref_id, no patch), and doff holds the part's n + 1
+// global output starts, dbase = the part's first: the tile is relative to it.
+template <bool kMerge>
 __global__ __launch_bounds__(kSortThreads) void k_sort_gather(const uint8_t* __restrict__ u,
                                                               const uint64_t* __restrict__ rec_pos,
                                                               const int32_t* __restrict__ ref_id,
                                                               const uint32_t* __restrict__ perm,
                                                               const uint64_t* __restrict__ doff, uint32_t n,
-                                                              uint64_t total, uint8_t* __restrict__ dst) {
+                                                              uint64_t total, uint8_t* __restrict__ dst,
+                                                              uint64_t dbase) {
   __shared__ uint64_t t_off[kSortTable];
   __shared__ uint64_t t_src[kSortTable];
   const uint64_t t0 = (uint64_t)blockIdx.x * kSortTile;
@@ -99,17 +107,21 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_gather(const uint8_t* __r
   uint32_t lo = 0, hi = n;
   while (hi - lo > 1) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (doff[mid] <= t0) lo = mid; else hi = mid;
+    if (doff[mid] - (kMerge ? dbase : 0) <= t0) lo = mid; else hi = mid;
   }
   const uint32_t j0 = lo;
   for (uint32_t k = threadIdx.x; k < kSortTable; k += kSortThreads) {
     const uint64_t j = (uint64_t)j0 + k;
     uint64_t o = ~0ull, s = 0;
     if (j <= n) {
-      o = doff[j];  // (a start at or past t1 ends the tile's last record; later ones are never searched for)
+      o = doff[j] - (kMerge ? dbase : 0);  // (a start at or past t1 ends the tile's last record; later ones are never searched for)
       if (j < n && o < t1) {
-        const uint32_t r = perm[j];
-        s = rec_pos[r] | (ref_id[r] < 0 ? kSortUnplaced : 0);
+        if constexpr (kMerge) {
+          s = rec_pos[j];
+        } else {
+          const uint32_t r = perm[j];
+          s = rec_pos[r] | (ref_id[r] < 0 ? kSortUnplaced : 0);
+        }
       }
     }
     t_off[k] = o;
@@ -199,8 +211,25 @@ hipError_t launch_sort_gather(const uint8_t* u, const uint64_t* rec_pos, const i
                               const uint64_t* doff, uint64_t n, uint64_t total, uint8_t* dst, hipStream_t s) {
   if (n == 0 || total == 0) return hipSuccess;
   const uint64_t tiles = (total + kSortTile - 1) / kSortTile;
-  hipLaunchKernelGGL(k_sort_gather, dim3((unsigned)tiles), dim3(kSortThreads), 0, s, u, rec_pos, ref_id, perm, doff,
-                     (uint32_t)n, total, dst);
+  hipLaunchKernelGGL(k_sort_gather<false>, dim3((unsigned)tiles), dim3(kSortThreads), 0, s, u, rec_pos, ref_id, perm,
+                     doff, (uint32_t)n, total, dst, (uint64_t)0);
+  return hipGetLastError();
+}
+
+hipError_t launch_sort_words(const Columns& col, uint64_t n, int order, uint64_t* word, uint32_t* len, uint32_t* iota,
+                             hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sort_words, dim3(blocks_for(n)), dim3(kSortThreads), 0, s, col.key, col.ref_id, col.pos,
+                     col.rest_len, n, order, word, len, iota);
+  return hipGetLastError();
+}
+
+hipError_t launch_merge_gather(const uint8_t* u, const uint64_t* src_pos, const uint64_t* doff, uint64_t n,
+                               uint64_t dbase, uint64_t total, uint8_t* dst, hipStream_t s) {
+  if (n == 0 || total == 0) return hipSuccess;
+  const uint64_t tiles = (total + kSortTile - 1) / kSortTile;
+  hipLaunchKernelGGL(k_sort_gather<true>, dim3((unsigned)tiles), dim3(kSortThreads), 0, s, u, src_pos, nullptr,
+                     nullptr, doff, (uint32_t)n, total, dst, dbase);
   return hipGetLastError();
 }
 

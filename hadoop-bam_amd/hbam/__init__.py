@@ -136,6 +136,12 @@ _sig("hbam_encode_writables", C.c_int, [P, P, u64, P, C.POINTER(u64)])
 _sig("hbam_sort_writables", C.c_int, [P, i32, P, u64, P, P, C.POINTER(u64)])
 _sig("hbam_decode_writables", C.c_int, [P, P, u64, P, u64, C.POINTER(Batch)])
 _sig("hbam_open_codec", C.c_int, [C.POINTER(Opts), C.POINTER(P)])
+_sig("hbam_merge_begin", C.c_int, [P, i32])
+_sig("hbam_merge_add_run", C.c_int, [P, P, u64, P, u64, P])
+_sig("hbam_merge_plan", C.c_int, [P, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
+_sig("hbam_merge_next", C.c_int, [P, P, u64, P, P, C.POINTER(u64), C.POINTER(u64)])
+_sig("hbam_merge_end", C.c_int, [P])
+_sig("hbam_merge_times", C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_float)])
 _sig("hbam_gpu_encode_writables", C.c_int, [P, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_sort_writables", C.c_int, [P, i32, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_fetch_encoded", C.c_int, [P, u64, u64, P])
@@ -320,9 +326,96 @@ class PinnedBuffer:
         self.close()
 
 
-class Codec:
+class _Merge:
+    """hbam_merge_*: the merge of sorted runs of SAMRecordWritable encodings
+    on the ctx self._h (Hadoop's reduce-side merge; shared by Codec and
+    BamFile).  The runs' bytes stay in host memory; the order is planned and
+    every part gathered on the GPU."""
+
+    def _merge_err(self, rc):
+        return HbamError(rc, _L.hbam_last_error(self._h).decode(errors="replace"))
+
+    def merge_begin(self, order="key"):
+        rc = _L.hbam_merge_begin(self._h, SORT_ORDERS.get(order, order))
+        if rc != OK:
+            raise self._merge_err(rc)
+        self._merge_keep = []
+
+    def merge_add_run(self, enc, offs, words=None):
+        """One sorted run: enc = its encodings (bytes, bytearray, a NumPy uint8
+        array or an np.memmap: not copied, a reference is kept until
+        merge_end), offs = n + 1 record starts with offs[n] = len(enc), words
+        = its n sort words (hbam.sort.sort_words) or None: computed on the GPU
+        from the encodings."""
+        if isinstance(enc, np.ndarray):
+            buf = enc if enc.dtype == np.uint8 and enc.ndim == 1 and enc.flags.c_contiguous else \
+                np.ascontiguousarray(enc).view(np.uint8).reshape(-1)
+        else:
+            buf = np.frombuffer(enc, np.uint8)
+        o = np.ascontiguousarray(offs, np.uint64)
+        if len(o) == 0:
+            raise HbamError(E_ARG, "merge_add_run: offs needs n + 1 entries")
+        w = None if words is None else np.ascontiguousarray(words, np.uint64)
+        if w is not None and len(w) != len(o) - 1:
+            raise HbamError(E_ARG, "merge_add_run: words needs one entry per record")
+        keep = (enc, buf, o, w)
+        rc = _L.hbam_merge_add_run(self._h, buf.ctypes.data if len(buf) else None, len(buf), o.ctypes.data,
+                                   len(o) - 1, w.ctypes.data if w is not None and len(w) else None)
+        if rc != OK:
+            raise self._merge_err(rc)
+        self._merge_keep.append(keep)
+
+    def merge_plan(self, part_bytes=0):
+        """(parts, records, bytes) of the merged output, cut every part_bytes (0: 1 GiB)."""
+        a, b, c = u64(), u64(), u64()
+        rc = _L.hbam_merge_plan(self._h, part_bytes, C.byref(a), C.byref(b), C.byref(c))
+        if rc != OK:
+            raise self._merge_err(rc)
+        return a.value, b.value, c.value
+
+    def merge_next(self):
+        """The next part: (bytes, offs[u64, n + 1] relative to the part,
+        src[u64, n] = run << 32 | record index in that run); None after the last."""
+        n, ln = u64(), u64()
+        rc = _L.hbam_merge_next(self._h, None, 0, None, None, C.byref(n), C.byref(ln))
+        if rc != OK:
+            raise self._merge_err(rc)
+        if n.value == 0:
+            return None
+        out = C.create_string_buffer(max(ln.value, 1))
+        offs = np.zeros(n.value + 1, np.uint64)
+        src = np.zeros(n.value, np.uint64)
+        rc = _L.hbam_merge_next(self._h, out, ln.value, offs.ctypes.data, src.ctypes.data, C.byref(n), C.byref(ln))
+        if rc != OK:
+            raise self._merge_err(rc)
+        return out.raw[:ln.value], offs, src
+
+    def merge_end(self):
+        if self._h:
+            _L.hbam_merge_end(self._h)
+        self._merge_keep = []
+
+    def merge_times(self):
+        """(plan_ms[3], part_ms[3]) of the open merge (hbam_merge_times)."""
+        a, b = (C.c_float * 3)(), (C.c_float * 3)()
+        rc = _L.hbam_merge_times(self._h, a, b)
+        if rc != OK:
+            raise self._merge_err(rc)
+        return list(a), list(b)
+
+    def iter_merged(self, part_bytes=0):
+        """merge_plan, then every part in turn."""
+        self.merge_plan(part_bytes)
+        while True:
+            part = self.merge_next()
+            if part is None:
+                return
+            yield part
+
+
+class Codec(_Merge):
     """SAMRecordWritable.readFields in bulk on a GPU with no file open
-    (a reducer's view: hbam_open_codec + hbam_decode_writables)."""
+    (a reducer's view: hbam_open_codec + hbam_decode_writables + hbam_merge_*)."""
 
     def __init__(self, device=0):
         self._h = P()
@@ -366,7 +459,7 @@ def reader_callback(read):
     return READ_FN(cb)
 
 
-class BamFile:
+class BamFile(_Merge):
     """An opened BAM (or plain BGZF with bam=False) on one GPU.  path= opens
     a file split-locally (only the windows a decode needs are read, with
     pread); reader= + size= reads through a positioned-read callback

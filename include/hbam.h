@@ -382,6 +382,67 @@ int hbam_decode_writables(hbam_ctx *ctx, const void *buf, uint64_t len, const ui
  * hbam_decode_writables. */
 int hbam_open_codec(const hbam_opts *opts, hbam_ctx **out);
 
+/* ---- Merge of sorted runs (the reduce side of the sort job) ---- */
+/* Hadoop's reduce-side merge of the sorted map outputs (the shuffle's
+ * Merger.merge feeding the reducer of the reference's sort job), for k runs of
+ * SAMRecordWritable encodings that are each sorted by one hbam_sort_writables
+ * order: the output is the order one stable sort of the concatenated runs
+ * would give.  Ties go to the earlier run, then to the earlier record of a
+ * run.  The order is planned and every part gathered on the GPU; the run bytes
+ * stay in the caller's host memory (which may be an mmap of a spill file), only
+ * the sort word and the framing of every record live in HBM, so the runs' total
+ * size is not bounded by HBM.  Works on a file ctx or a codec ctx; one merge
+ * per ctx at a time.  The ctx serves every other call meanwhile.
+ *
+ * hbam_merge_begin: order = HBAM_SORT_KEY / HBAM_SORT_COORDINATE; another value
+ * -> HBAM_E_ARG; a merge already open on ctx -> HBAM_E_STATE.
+ *
+ * hbam_merge_add_run: run = buf[0, len), record i = buf[offs[i], offs[i+1])
+ * (offs: n + 1 entries, offs[n] == len).  buf and offs stay the caller's and
+ * buf must stay valid and unchanged until hbam_merge_end.  n == 0 is allowed.
+ * words: the n sort words of the run's records, exactly hbam_sort_writables':
+ *   HBAM_SORT_KEY         (uint64)key ^ 1 << 63
+ *   HBAM_SORT_COORDINATE  (uint64)(uint32)refID << 32 | (uint32)(pos + 1)
+ * or NULL: computed on the GPU from the encodings (hbam_decode_writables of
+ * the run, whose errors apply to a bad value; the ctx's last batch becomes that
+ * decode's).  With words given the last batch is untouched: a file ctx can
+ * alternate hbam_decode_span, hbam_sort_writables and hbam_merge_add_run.
+ * Checked on the GPU, HBAM_E_ARG: offsets that do not increase, a record
+ * shorter than 36 bytes or ending past len, offs[n] != len, words that are not
+ * non-decreasing (hbam_last_error names the run and the first offending
+ * record).  A total of 2^31 - 1 records or more -> HBAM_E_ARG.  A refused run
+ * is not added.  After hbam_merge_plan, or with no merge open -> HBAM_E_STATE.
+ *
+ * hbam_merge_plan (once): sorts, cuts the output into parts and reports the
+ * number of parts, the total records and the total bytes.  Output record j
+ * belongs to part (its output start) / part_bytes (0: 1 GiB); parts in which no
+ * record starts do not exist, so a part holds at least one record and fewer
+ * than part_bytes + the longest record bytes.  No runs, or only empty ones:
+ * 0 / 0 / 0.
+ *
+ * hbam_merge_next: the next part.  out == NULL sizes it: *n and *len are set,
+ * nothing is launched and the part stays.  Otherwise out receives its *len
+ * bytes, offs (NULL or n + 1 entries) the record starts relative to the part,
+ * offs[n] = *len, src (NULL or n entries) run << 32 | record index in that run
+ * (hbam_sort_writables' perm), and the merge moves on.  cap < *len ->
+ * HBAM_E_ARG, the part stays.  Past the last part: HBAM_OK with *n = *len = 0.
+ * Before hbam_merge_plan -> HBAM_E_STATE.
+ *
+ * hbam_merge_end frees the merge's device state (HBAM_OK with none open);
+ * hbam_close ends an open merge. */
+int hbam_merge_begin(hbam_ctx *ctx, int32_t order);
+int hbam_merge_add_run(hbam_ctx *ctx, const uint8_t *buf, uint64_t len, const uint64_t *offs, uint64_t n,
+                       const uint64_t *words /* NULL: computed from the encodings */);
+int hbam_merge_plan(hbam_ctx *ctx, uint64_t part_bytes /* 0: 1 GiB */, uint64_t *n_parts, uint64_t *n_records,
+                    uint64_t *bytes);
+int hbam_merge_next(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *offs, uint64_t *src, uint64_t *n,
+                    uint64_t *len);
+int hbam_merge_end(hbam_ctx *ctx);
+/* Measurement: HIP-event milliseconds of the open merge's plan (radix sort,
+ * output starts, parts + cuts) and of its last written part (H2D of the
+ * slices, source table + gather, D2H).  No merge open -> HBAM_E_STATE. */
+int hbam_merge_times(hbam_ctx *ctx, float plan_ms[3], float part_ms[3]);
+
 /* ---- BGZF write path ---- */
 #define HBAM_BGZF_EOF 1 /* append the 28-byte BGZF EOF terminator (BlockCompressedOutputStream.close) */
 /* [htsjdk] BlockCompressedOutputStream.write + deflateBlock + writeGzipBlock

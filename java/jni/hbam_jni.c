@@ -176,8 +176,42 @@ JNIEXPORT jlong FN(openReader)(JNIEnv *env, jclass c, jlong size, jobject reader
   return (jlong)(intptr_t)ctx;
 }
 
+/* ---- hbam_merge_*: the runs of an open merge stay referenced until mergeEnd ---- */
+struct jrun {
+  hbam_ctx *ctx;
+  jobject buf;    /* global ref to the run's direct ByteBuffer */
+  uint64_t *offs; /* the run's n + 1 offsets (the library reads them at add time; kept with the run) */
+  struct jrun *next;
+};
+static struct jrun *g_runs = NULL;
+static pthread_mutex_t g_runs_mu = PTHREAD_MUTEX_INITIALIZER;
+
+static void drop_runs(JNIEnv *env, hbam_ctx *ctx) {
+  pthread_mutex_lock(&g_runs_mu);
+  struct jrun **pp = &g_runs, *mine = NULL;
+  while (*pp) {
+    if ((*pp)->ctx == ctx) {
+      struct jrun *r = *pp;
+      *pp = r->next;
+      r->next = mine;
+      mine = r;
+    } else {
+      pp = &(*pp)->next;
+    }
+  }
+  pthread_mutex_unlock(&g_runs_mu);
+  while (mine) {
+    struct jrun *r = mine;
+    mine = r->next;
+    (*env)->DeleteGlobalRef(env, r->buf);
+    free(r->offs);
+    free(r);
+  }
+}
+
 JNIEXPORT void FN(close)(JNIEnv *env, jclass c, jlong h) {
-  hbam_close(CTX(h)); /* joins the ctx's threads: no read after this */
+  hbam_close(CTX(h)); /* joins the ctx's threads: no read after this; ends an open merge */
+  drop_runs(env, CTX(h));
   pthread_mutex_lock(&g_readers_mu);
   struct jreader **pp = &g_readers, *r = NULL;
   while (*pp && (*pp)->ctx != CTX(h)) pp = &(*pp)->next;
@@ -505,6 +539,102 @@ JNIEXPORT jlong FN(sortWritables)(JNIEnv *env, jclass c, jlong h, jint order, jo
   }
   free(o);
   return (jlong)len;
+}
+
+JNIEXPORT void FN(mergeBegin)(JNIEnv *env, jclass c, jlong h, jint order) {
+  int rc = hbam_merge_begin(CTX(h), order);
+  if (rc != HBAM_OK) throw_for(env, rc, hbam_last_error(CTX(h)));
+}
+
+JNIEXPORT void FN(mergeAddRun)(JNIEnv *env, jclass c, jlong h, jobject buf, jlongArray offs, jlongArray words) {
+  jsize no = 0, nw = 0;
+  const uint8_t *p = buf ? (const uint8_t *)(*env)->GetDirectBufferAddress(env, buf) : NULL;
+  if (!p || !offs) {
+    throw_for(env, HBAM_E_ARG, "mergeAddRun needs a direct buffer and its offsets");
+    return;
+  }
+  const uint64_t len = (uint64_t)(*env)->GetDirectBufferCapacity(env, buf);
+  uint64_t *o = from_longs(env, offs, &no);
+  if (!o) return;
+  uint64_t *w = NULL;
+  if (words && !(w = from_longs(env, words, &nw))) {
+    free(o);
+    return;
+  }
+  struct jrun *r = (struct jrun *)calloc(1, sizeof *r);
+  if (!r || no < 1 || (words && nw != no - 1)) {
+    throw_for(env, r ? HBAM_E_ARG : HBAM_E_NOMEM, r ? "offs needs n + 1 entries, words n" : "out of memory");
+    free(o);
+    free(w);
+    free(r);
+    return;
+  }
+  r->ctx = CTX(h);
+  r->offs = o;
+  r->buf = (*env)->NewGlobalRef(env, buf);
+  int rc = r->buf ? hbam_merge_add_run(CTX(h), p, len, o, (uint64_t)(no - 1), w) : HBAM_E_NOMEM;
+  free(w); /* copied to the device by the call */
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, r->buf ? hbam_last_error(CTX(h)) : "out of memory");
+    if (r->buf) (*env)->DeleteGlobalRef(env, r->buf);
+    free(o);
+    free(r);
+    return;
+  }
+  pthread_mutex_lock(&g_runs_mu);
+  r->next = g_runs;
+  g_runs = r;
+  pthread_mutex_unlock(&g_runs_mu);
+}
+
+JNIEXPORT jlongArray FN(mergePlan)(JNIEnv *env, jclass c, jlong h, jlong partBytes) {
+  uint64_t v[3] = {0, 0, 0};
+  int rc = hbam_merge_plan(CTX(h), (uint64_t)partBytes, &v[0], &v[1], &v[2]);
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, hbam_last_error(CTX(h)));
+    return NULL;
+  }
+  return to_longs(env, v, 3);
+}
+
+JNIEXPORT jlongArray FN(mergeNext)(JNIEnv *env, jclass c, jlong h, jobject out, jlongArray offs, jlongArray src) {
+  uint64_t v[2] = {0, 0};
+  uint8_t *dst = out ? (uint8_t *)(*env)->GetDirectBufferAddress(env, out) : NULL;
+  const uint64_t cap = out ? (uint64_t)(*env)->GetDirectBufferCapacity(env, out) : 0;
+  const jsize no = dst && offs ? (*env)->GetArrayLength(env, offs) : 0;
+  const jsize ns = dst && src ? (*env)->GetArrayLength(env, src) : 0;
+  /* the part's size first: the arrays must hold n + 1 and n entries before the library writes them */
+  int rc = hbam_merge_next(CTX(h), NULL, 0, NULL, NULL, &v[0], &v[1]);
+  if (rc == HBAM_OK && dst && v[0]) {
+    if ((offs && (uint64_t)no < v[0] + 1) || (src && (uint64_t)ns < v[0])) {
+      throw_for(env, HBAM_E_ARG, "mergeNext: offs needs n + 1 entries and src n");
+      return NULL;
+    }
+    uint64_t *o = offs ? (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(v[0] + 1)) : NULL;
+    uint64_t *s = src ? (uint64_t *)malloc(sizeof(uint64_t) * (size_t)v[0]) : NULL;
+    if ((offs && !o) || (src && !s)) {
+      free(o);
+      free(s);
+      throw_for(env, HBAM_E_NOMEM, "out of memory");
+      return NULL;
+    }
+    rc = hbam_merge_next(CTX(h), dst, cap, o, s, &v[0], &v[1]);
+    if (rc == HBAM_OK && o) (*env)->SetLongArrayRegion(env, offs, 0, (jsize)(v[0] + 1), (const jlong *)o);
+    if (rc == HBAM_OK && s) (*env)->SetLongArrayRegion(env, src, 0, (jsize)v[0], (const jlong *)s);
+    free(o);
+    free(s);
+  }
+  if (rc != HBAM_OK) {
+    throw_for(env, rc, hbam_last_error(CTX(h)));
+    return NULL;
+  }
+  return to_longs(env, v, 2);
+}
+
+JNIEXPORT void FN(mergeEnd)(JNIEnv *env, jclass c, jlong h) {
+  int rc = hbam_merge_end(CTX(h));
+  drop_runs(env, CTX(h));
+  if (rc != HBAM_OK) throw_for(env, rc, hbam_last_error(CTX(h)));
 }
 
 JNIEXPORT jlong FN(openCodec)(JNIEnv *env, jclass c, jint device) {

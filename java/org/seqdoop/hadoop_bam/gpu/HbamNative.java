@@ -214,6 +214,36 @@ public final class HbamNative {
   public static native long sortWritables(long ctx, int order, ByteBuffer out, long[] offs, int[] perm)
       throws IOException;
 
+  /**
+   * hbam_merge_begin: open the merge of sorted runs on ctx (a file or a codec
+   * context) -- the reduce side of the sort job, Hadoop's merge of the sorted
+   * map outputs.  order: SORT_KEY or SORT_COORDINATE.
+   */
+  public static native void mergeBegin(long ctx, int order) throws IOException;
+
+  /**
+   * hbam_merge_add_run: one sorted run of SAMRecordWritable encodings in a
+   * direct buffer (not copied: the glue holds a global reference to it until
+   * mergeEnd), offs = its n + 1 record starts, words = its n sort words or null
+   * (computed on the GPU from the encodings).  A run that is not sorted or
+   * badly framed: IllegalArgumentException.
+   */
+  public static native void mergeAddRun(long ctx, ByteBuffer run, long[] offs, long[] words) throws IOException;
+
+  /** hbam_merge_plan: {parts, records, bytes} of the merged output cut every partBytes (0: 1 GiB). */
+  public static native long[] mergePlan(long ctx, long partBytes) throws IOException;
+
+  /**
+   * hbam_merge_next: {n, len} of the next part; out == null only sizes it.
+   * Otherwise out (direct) receives its bytes, offs (null or n + 1) the record
+   * starts in the part, src (null or n) run &lt;&lt; 32 | record index, and the merge
+   * moves on.  {0, 0} after the last part.
+   */
+  public static native long[] mergeNext(long ctx, ByteBuffer out, long[] offs, long[] src) throws IOException;
+
+  /** hbam_merge_end: free the merge's device state and the references to its runs. */
+  public static native void mergeEnd(long ctx) throws IOException;
+
   /** hbam_open_codec: a device context with no file (reduce side). */
   public static native long openCodec(int device) throws IOException;
 
