@@ -615,7 +615,7 @@ int hbam_sort_writables(hbam_ctx* ctx, int32_t order, uint8_t* out, uint64_t cap
     ctx->err = "hbam_sort_writables needs a one-window batch from hbam_decode_span";
     return HBAM_E_STATE;
   }
-  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE) {
+  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE && order != HBAM_SORT_QUERYNAME) {
     ctx->err = "unknown sort order " + std::to_string(order);
     return HBAM_E_ARG;
   }
@@ -698,7 +698,7 @@ int hbam_merge_begin(hbam_ctx* ctx, int32_t order) {
     ctx->err = "hbam_merge_begin: a merge is already open on this ctx (hbam_merge_end closes it)";
     return HBAM_E_STATE;
   }
-  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE) {
+  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE && order != HBAM_SORT_QUERYNAME) {
     ctx->err = "unknown sort order " + std::to_string(order);
     return HBAM_E_ARG;
   }
@@ -715,6 +715,11 @@ int hbam_merge_add_run(hbam_ctx* ctx, const uint8_t* buf, uint64_t len, const ui
     return HBAM_E_STATE;
   }
   hbam::Merger& m = *ctx->merge;
+  if (m.order() == HBAM_SORT_QUERYNAME && words) {
+    ctx->err = "hbam_merge_add_run: words must be NULL in queryname order (there is no sort word: the names are "
+               "read from the encodings)";
+    return HBAM_E_ARG;
+  }
   int rc = m.begin_run(buf, len, offs, n);
   if (rc != HBAM_OK) {
     ctx->err = "hbam_merge_add_run: " + m.error();
@@ -726,7 +731,7 @@ int hbam_merge_add_run(hbam_ctx* ctx, const uint8_t* buf, uint64_t len, const ui
     rc = hbam_decode_writables(ctx, buf, len, offs, n, &b);
     if (rc != HBAM_OK) return rc;
   }
-  rc = m.finish_run(words, words ? nullptr : &ctx->wspan.col);
+  rc = m.finish_run(words, words || !n ? nullptr : &ctx->wspan);
   if (rc != HBAM_OK) ctx->err = "hbam_merge_add_run: " + m.error();
   return rc;
 }
@@ -759,6 +764,14 @@ int hbam_merge_next(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, u
 int hbam_merge_end(hbam_ctx* ctx) {
   if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
   ctx->merge.reset();
+  return HBAM_OK;
+}
+
+int hbam_sort_name_counters(hbam_ctx* ctx, uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  const hbam::Pipeline& p = ctx->f ? ctx->f->pipe() : *ctx->codec;
+  for (int i = 0; i < 3; ++i) out[i] = p.name_counters()[i];
   return HBAM_OK;
 }
 
@@ -1290,6 +1303,20 @@ int hbam_gpu_sort_writables(hbam_gpu* g, int32_t order, int32_t iters, float ms[
   }
   g->enc_bytes = nb;
   *bytes = nb;
+  return HBAM_OK;
+}
+
+int hbam_gpu_sort_name_counters(hbam_gpu* g, uint64_t out[3]) {
+  out[0] = out[1] = out[2] = 0;
+  if (!g->f) return HBAM_E_STATE;
+  for (int i = 0; i < 3; ++i) out[i] = g->f->pipe().name_counters()[i];
+  return HBAM_OK;
+}
+
+int hbam_gpu_sort_name_times(hbam_gpu* g, float ms[3]) {
+  ms[0] = ms[1] = ms[2] = 0;
+  if (!g->f) return HBAM_E_STATE;
+  for (int i = 0; i < 3; ++i) ms[i] = g->f->pipe().name_times()[i];
   return HBAM_OK;
 }
 

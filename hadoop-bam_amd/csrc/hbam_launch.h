@@ -185,6 +185,47 @@ hipError_t launch_sort_gather(const uint8_t* u, const uint64_t* rec_pos, const i
 // k_sort_words alone: the sort words, encoded lengths and iota of n decoded records
 hipError_t launch_sort_words(const Columns& col, uint64_t n, int order, uint64_t* word, uint32_t* len, uint32_t* iota,
                              hipStream_t s);
+// Queryname order (hbam_names.hip): the name = name_len bytes at base +
+// name_pos, zero-extended and compared as unsigned bytes, then the tie word
+// (2 * mate rank + secondary/supplementary, from the flag), then the input
+// order.  An LSD radix sort over the name's 8-byte big-endian chunks.
+enum : int { kSortQueryname = 3 };  // (2 is not an order)
+constexpr uint32_t kNameChunks = 32;  // ceil(255 / 8): l_read_name is a byte
+// the census buffer: two halves (OR-like words preset 0, AND-like words preset
+// ~0) of kNameChunks chunk words, the tie word and the most / fewest chunks
+constexpr uint32_t kNameCensusTie = kNameChunks, kNameCensusChunks = kNameChunks + 1;
+constexpr uint32_t kNameCensusHalf = kNameChunks + 2, kNameCensusWords = 2 * kNameCensusHalf;
+struct NameOrderStats {
+  uint64_t chunks_present = 0;  // the most chunks of a name
+  uint64_t chunks_sorted = 0;   // chunk indices in which the names differ: one radix sort each
+  uint64_t bits_sorted = 0;     // the bits those sorts cover (the tie word's pass is not counted)
+};
+// device -> host copy of `bytes` that has landed when it returns (Pipeline::rb + rb_sync)
+typedef hipError_t (*NameReadback)(void* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
+// name_pos = rec_pos + 36, name_len = min(l_read_name, rest_len), tie = the flag's tie word, of n decoded
+// records; len (nullptr or n u32) = their encoded lengths, 36 + rest_len
+hipError_t launch_name_refs(const uint64_t* rec_pos, const Columns& col, uint64_t n, uint64_t* name_pos,
+                            uint8_t* name_len, uint8_t* tie, uint32_t* len, hipStream_t s);
+// perm[j] = the index of the j-th record in queryname order.  tmp: sort_tmp_bytes(n);
+// word, word2: n u64; scratch, perm: n u32; census: kNameCensusWords u64.  Every
+// aligned 8-byte word that holds a byte of a name must be readable.
+// Measurement: full = sort every chunk present over all 64 bits (the census
+// still runs; the order is the same); after_census / after_tie (or nullptr) are
+// recorded behind the census read-back and behind the tie word's pass.
+hipError_t launch_name_order(void* tmp, size_t tmp_bytes, const uint8_t* base, const uint64_t* name_pos,
+                             const uint8_t* name_len, const uint8_t* tie, uint64_t n, uint64_t* word,
+                             uint64_t* word2, uint32_t* scratch, uint32_t* perm, uint64_t* census,
+                             NameReadback rb, void* rb_ctx, NameOrderStats* stats, hipStream_t s, bool full = false,
+                             hipEvent_t after_census = nullptr, hipEvent_t after_tie = nullptr);
+// *bad (preset ~0) = min over the records i > 0 whose (name, tie) is below record i - 1's
+hipError_t launch_name_sorted(const uint8_t* base, const uint64_t* name_pos, const uint8_t* name_len,
+                              const uint8_t* tie, uint64_t n, unsigned long long* bad, hipStream_t s);
+// at = the exclusive sum of name_len over n + 1 entries (at[n] = the names' bytes); len64, at: n + 1 u64
+hipError_t launch_name_starts(void* tmp, size_t tmp_bytes, const uint8_t* name_len, uint64_t n, uint64_t* len64,
+                              uint64_t* at, hipStream_t s);
+// the names copied back to back: dst[dst_base + at[i] ..) = the name at src + name_pos[i]; name_pos[i] = dst_base + at[i]
+hipError_t launch_name_pack(const uint8_t* src, uint64_t* name_pos, const uint8_t* name_len, const uint64_t* at,
+                            uint64_t n, uint8_t* dst, uint64_t dst_base, hipStream_t s);
 // Merge of k sorted runs of SAMRecordWritable encodings (hbam_merge.hip), total
 // records n < 2^31 - 1.  A record's global index is run-major: run_base[r] + i
 // (run_base: k + 1 u64).  Every run's n_r + 1 offsets lie back to back in one

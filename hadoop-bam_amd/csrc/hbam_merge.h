@@ -3,7 +3,10 @@
 // of the sorted map outputs.  The run bytes stay in the caller's host memory;
 // the sort word, the framing and the order of every record live in HBM, in
 // buffers this object owns (never the Pipeline's sort_* temporaries: a
-// sort_writables between two runs leaves them alone).  The order is planned
+// sort_writables between two runs leaves them alone).  In queryname order there
+// is no sort word: every record's name bytes are kept instead, packed, with
+// where they start, their length and the tie word (name bytes + 10 B per
+// record until the merge ends).  The order is planned
 // once on the device (kernels of hbam_merge.hip); each part is then staged
 // host -> HBM as k contiguous slices, gathered and copied back.
 #pragma once
@@ -29,9 +32,11 @@ class Merger {
   // A run in two steps, nothing kept if either fails.  begin_run: the framing
   // to HBM and checked (offs: n + 1 entries, offs[n] == len).  finish_run: the
   // words -- the caller's, or k_sort_words of the columns of a decode of the
-  // same values (col) -- checked to be non-decreasing; the run is then added.
+  // same values (span) -- checked to be non-decreasing; the run is then added.
+  // Queryname order: words == nullptr; the names are read from the decode's
+  // copy of the run (span->data), checked to be in order and packed.
   int begin_run(const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n);
-  int finish_run(const uint64_t* words, const Columns* col);
+  int finish_run(const uint64_t* words, const SpanDev* span);
   // The order, the output starts, the parts (part_bytes > 0) and the cut table.
   int plan(uint64_t part_bytes, uint64_t* n_parts, uint64_t* n_records, uint64_t* bytes);
   // The next part: out == nullptr sizes it (*n, *len) and keeps it; else its
@@ -52,6 +57,7 @@ class Merger {
   };
   int fail(int code, const std::string& msg);
   int hip_check(hipError_t e, const char* what);
+  int finish_run_names(const Run& r, const SpanDev& span);
 
   Pipeline& p_;
   int order_;
@@ -68,6 +74,11 @@ class Merger {
   DevBuf<uint64_t> off_, word_;
   DevBuf<uint32_t> len_, idx_;
   DevBuf<unsigned long long> bad_;
+  // queryname order, alive to the end: the names back to back (names_used_
+  // bytes, 8 readable past them), each record's start in them, length and tie word
+  DevBuf<uint8_t> names_, name_len_, tie_;
+  DevBuf<uint64_t> name_pos_;
+  uint64_t names_used_ = 0;
   // the plan: sorted words, output starts (+ the lengths they are summed from),
   // order and its inverse, part flags / numbers, hipcub storage
   DevBuf<uint64_t> word2_, slen_, doff_;

@@ -18,6 +18,7 @@ Merger::Merger(Pipeline& p, int order) : p_(p), order_(order) {
   off_.owner = word_.owner = word2_.owner = slen_.owner = doff_.owner = o;
   len_.owner = idx_.owner = perm_.owner = rank_.owner = flag_.owner = num_.owner = o;
   bad_.owner = o;
+  names_.owner = name_len_.owner = tie_.owner = name_pos_.owner = o;
   tmp_.owner = stage_.owner = out_.owner = o;
   run_base_d_.owner = part_start_d_.owner = slice_base_d_.owner = src_pos_.owner = src_id_.owner = o;
   part_offs_.owner = o;
@@ -60,7 +61,13 @@ int Merger::begin_run(const uint8_t* buf, uint64_t len, const uint64_t* offs, ui
   const uint64_t k = runs_.size();
   // the run's n + 1 offsets behind the earlier runs' (run r's start at run_base[r] + r)
   MCHK(off_.grow(total_ + k + n + 1));
-  MCHK(word_.grow(std::max<uint64_t>(total_ + n, 1)));
+  if (order_ == kSortQueryname) {
+    MCHK(name_pos_.grow(std::max<uint64_t>(total_ + n, 1)));
+    MCHK(name_len_.grow(std::max<uint64_t>(total_ + n, 1)));
+    MCHK(tie_.grow(std::max<uint64_t>(total_ + n, 1)));
+  } else {
+    MCHK(word_.grow(std::max<uint64_t>(total_ + n, 1)));
+  }
   MCHK(len_.grow(std::max<uint64_t>(total_ + n, 1)));
   MCHK(idx_.grow(std::max<uint64_t>(total_ + n, 1)));
   MCHK(bad_.reserve(2));
@@ -84,7 +91,41 @@ int Merger::begin_run(const uint8_t* buf, uint64_t len, const uint64_t* offs, ui
   return kOk;
 }
 
-int Merger::finish_run(const uint64_t* words, const Columns* col) {
+// The names of the run just decoded (span: its columns and its copy of the
+// bytes): references, the order check on the decode's copy, then the names
+// packed behind the earlier runs'.  Nothing of the run is kept before the check.
+int Merger::finish_run_names(const Run& r, const SpanDev& span) {
+  const std::string run = "run " + std::to_string(runs_.size());
+  if (!span.col.flag || !span.col.l_read_name || !span.data || span.n != r.n)
+    return fail(kErrState, run + ": no decoded columns");
+  hipStream_t s = p_.stream();
+  uint64_t* pos = name_pos_.p + total_;
+  uint8_t* len = name_len_.p + total_;
+  uint8_t* tie = tie_.p + total_;
+  MCHK(launch_name_refs(span.rec_pos, span.col, r.n, pos, len, tie, nullptr, s));
+  MCHK(hipMemsetAsync(bad_.p, 0xff, sizeof(unsigned long long), s));
+  MCHK(launch_name_sorted(span.data, pos, len, tie, r.n, bad_.p, s));
+  size_t tmp = 0;
+  MCHK(merge_tmp_bytes(r.n, &tmp));
+  MCHK(tmp_.reserve(tmp));
+  MCHK(word_.reserve(r.n + 1));
+  MCHK(word2_.reserve(r.n + 1));
+  MCHK(launch_name_starts(tmp_.p, tmp, len, r.n, word_.p, word2_.p, s));
+  unsigned long long bad = ~0ull;
+  uint64_t bytes = 0;
+  MCHK(p_.rb(&bad, bad_.p, sizeof bad, s));
+  MCHK(p_.rb(&bytes, word2_.p + r.n, 8, s));
+  MCHK(p_.rb_sync(s));
+  if (bad != ~0ull)
+    return fail(kErrArg, run + " is not sorted: record " + std::to_string(bad) + " sorts before record " +
+                             std::to_string(bad - 1));
+  MCHK(names_.grow(names_used_ + bytes + 8));
+  MCHK(launch_name_pack(span.data, pos, len, word2_.p, r.n, names_.p, names_used_, s));
+  names_used_ += bytes;
+  return kOk;
+}
+
+int Merger::finish_run(const uint64_t* words, const SpanDev* span) {
   if (!has_pending_) return fail(kErrState, "no run begun");
   has_pending_ = false;
   const Run r = pending_;
@@ -92,7 +133,13 @@ int Merger::finish_run(const uint64_t* words, const Columns* col) {
   MCHK(hipSetDevice(p_.device()));
   hipStream_t s = p_.stream();
   const uint64_t k = runs_.size();
-  if (r.n) {
+  const Columns* col = span ? &span->col : nullptr;
+  if (r.n && order_ == kSortQueryname) {
+    if (words) return fail(kErrArg, run + ": words given in queryname order");
+    if (!span) return fail(kErrState, run + ": no decoded columns");
+    const int rc = finish_run_names(r, *span);
+    if (rc != kOk) return rc;
+  } else if (r.n) {
     uint64_t* d_word = word_.p + total_;
     if (words) {
       MCHK(hipMemcpyAsync(d_word, words, r.n * 8, hipMemcpyHostToDevice, s));
@@ -135,7 +182,14 @@ int Merger::plan(uint64_t part_bytes, uint64_t* n_parts, uint64_t* n_records, ui
   MCHK(slen_.reserve(n + 1));
   MCHK(doff_.reserve(n + 1));
   MCHK(hipEventRecord(ev_[0], s));
-  MCHK(launch_merge_perm(tmp_.p, tmp, word_.p, word2_.p, idx_.p, perm_.p, n, s));
+  if (order_ == kSortQueryname) {
+    MCHK(word_.reserve(n));
+    const int rc = p_.name_order(tmp_.p, tmp, names_.p, name_pos_.p, name_len_.p, tie_.p, n, word_.p, word2_.p,
+                                 idx_.p, perm_.p);
+    if (rc != kOk) return fail(rc, p_.error());
+  } else {
+    MCHK(launch_merge_perm(tmp_.p, tmp, word_.p, word2_.p, idx_.p, perm_.p, n, s));
+  }
   MCHK(hipEventRecord(ev_[1], s));
   MCHK(launch_sort_offsets(tmp_.p, tmp, len_.p, perm_.p, n, slen_.p, doff_.p, s));
   MCHK(hipEventRecord(ev_[2], s));

@@ -67,8 +67,9 @@ Pipeline::Pipeline(int device) : device_(device) {
       tinfo_[0], tinfo_[1], flist_[0], flist_[1], pstats_, g_, x_, x2_, entry_, base_arr_, summary_, dead_, cand_, sorted_, isz_, ust_, cnt_, flags_,
       errv_, need_, rec_pos_, rec_voff_, rcand_, force_, wcnt_, counters_, list_, scan_tmp_, cols_, long_rec_,
       long_n_, wbuf_, woffs_, wbad_, scalars_, fuse_, sort_word_, sort_word2_, sort_slen_, sort_doff_, sort_len_,
-      sort_iota_, sort_perm_, sort_tmp_, seg_anchor_, seg_exit_, seg_cnt_, seg_off_);
+      sort_iota_, sort_perm_, sort_tmp_, name_pos_, name_census_, name_len_, name_tie_, seg_anchor_, seg_exit_, seg_cnt_, seg_off_);
   if (const char* e = getenv("HBAM_LOCATE_SEG")) locate_seg_ = strtoull(e, nullptr, 0);
+  if (const char* e = getenv("HBAM_NAME_FULL_PASSES")) name_full_ = strtoull(e, nullptr, 0) != 0;
   for (auto& e : ev_) (void)hipEventCreate(&e);
   for (auto& e : sync_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& e : tab_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
@@ -1386,7 +1387,8 @@ int Pipeline::sort_writables(const SpanDev& s, int order, uint64_t bytes, uint8_
   if (ms) ms[0] = ms[1] = ms[2] = 0;
   if (s.n == 0) return kOk;
   if (!s.col.ref_id || !s.col.key) return fail(kErrState, "span was not decoded in reader mode");
-  if (order != kSortKey && order != kSortCoordinate) return fail(kErrArg, "unknown sort order");
+  if (order != kSortKey && order != kSortCoordinate && order != kSortQueryname)
+    return fail(kErrArg, "unknown sort order");
   if (s.n >= 0x7fffffffull) return fail(kErrArg, "too many records to sort in one batch");
   HIPCHK(hipSetDevice(device_));
   const uint64_t n = s.n;
@@ -1402,8 +1404,18 @@ int Pipeline::sort_writables(const SpanDev& s, int order, uint64_t bytes, uint8_
   HIPCHK(sort_doff_.reserve(n + 1));
   const uint8_t* src = s.data ? s.data : du_.p;
   if (ms) HIPCHK(hipEventRecord(ev_[4], stream_));
-  HIPCHK(launch_sort_perm(sort_tmp_.p, tmp, s.col, n, order, sort_word_.p, sort_word2_.p, sort_len_.p, sort_iota_.p,
-                          sort_perm_.p, stream_));
+  if (order == kSortQueryname) {
+    HIPCHK(name_pos_.reserve(n));
+    HIPCHK(name_len_.reserve(n));
+    HIPCHK(name_tie_.reserve(n));
+    HIPCHK(launch_name_refs(s.rec_pos, s.col, n, name_pos_.p, name_len_.p, name_tie_.p, sort_len_.p, stream_));
+    const int rc = name_order(sort_tmp_.p, tmp, src, name_pos_.p, name_len_.p, name_tie_.p, n, sort_word_.p,
+                              sort_word2_.p, sort_iota_.p, sort_perm_.p, ms != nullptr);
+    if (rc != kOk) return rc;
+  } else {
+    HIPCHK(launch_sort_perm(sort_tmp_.p, tmp, s.col, n, order, sort_word_.p, sort_word2_.p, sort_len_.p, sort_iota_.p,
+                            sort_perm_.p, stream_));
+  }
   if (ms) HIPCHK(hipEventRecord(ev_[5], stream_));
   HIPCHK(launch_sort_offsets(sort_tmp_.p, tmp, sort_len_.p, sort_perm_.p, n, sort_slen_.p, sort_doff_.p, stream_));
   if (ms) HIPCHK(hipEventRecord(ev_[6], stream_));
@@ -1412,7 +1424,34 @@ int Pipeline::sort_writables(const SpanDev& s, int order, uint64_t bytes, uint8_
     HIPCHK(hipEventRecord(ev_[7], stream_));
     HIPCHK(hipEventSynchronize(ev_[7]));
     for (int k = 0; k < 3; ++k) HIPCHK(hipEventElapsedTime(&ms[k], ev_[4 + k], ev_[5 + k]));
+    if (order == kSortQueryname) {
+      HIPCHK(hipEventElapsedTime(&name_ms_[0], ev_[4], ev_[0]));
+      HIPCHK(hipEventElapsedTime(&name_ms_[1], ev_[0], ev_[1]));
+      HIPCHK(hipEventElapsedTime(&name_ms_[2], ev_[1], ev_[5]));
+    }
   }
+  return kOk;
+}
+
+namespace {
+hipError_t name_readback(void* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
+  Pipeline* p = static_cast<Pipeline*>(ctx);
+  const hipError_t e = p->rb(dst, src, bytes, s);
+  return e != hipSuccess ? e : p->rb_sync(s);
+}
+}  // namespace
+
+int Pipeline::name_order(void* tmp, size_t tmp_bytes, const uint8_t* base, const uint64_t* name_pos,
+                         const uint8_t* name_len, const uint8_t* tie, uint64_t n, uint64_t* word, uint64_t* word2,
+                         uint32_t* scratch, uint32_t* perm, bool timed) {
+  HIPCHK(name_census_.reserve(kNameCensusWords));
+  NameOrderStats st;
+  HIPCHK(launch_name_order(tmp, tmp_bytes, base, name_pos, name_len, tie, n, word, word2, scratch, perm,
+                           name_census_.p, name_readback, this, &st, stream_, name_full_, timed ? ev_[0] : nullptr,
+                           timed ? ev_[1] : nullptr));
+  name_counters_[0] = st.chunks_present;
+  name_counters_[1] = st.chunks_sorted;
+  name_counters_[2] = st.bits_sorted;
   return kOk;
 }
 

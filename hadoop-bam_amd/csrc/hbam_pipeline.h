@@ -293,12 +293,26 @@ class Pipeline {
   // times of the sort words + radix sort, the lengths + scan and the gather
   // (waits for the stream).
   int sort_writables(const SpanDev& span, int order, uint64_t bytes, uint8_t* dst, float* ms = nullptr);
+  // order kSortQueryname: the read name, then the flag's tie word (hbam_names.hip)
   const uint32_t* sort_perm() const { return sort_perm_.p; }
   const uint64_t* sort_offsets() const { return sort_doff_.p; }
   // SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) of n values
   // framed by offs in host memory (value i = buf[offs[i], offs[i+1]), the
   // last ends at len): SoA columns + keys; out->n stops at the first bad value.
   int decode_writables(const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n, SpanDev* out);
+  // launch_name_order on this pipeline's stream with its read-back queue:
+  // perm = the queryname order of n records named by (base, name_pos, name_len,
+  // tie).  The caller owns every buffer (sizes: hbam_launch.h).  The counters
+  // of the last one: name_counters (chunks present, chunks sorted, bits sorted).
+  // timed: ev_[0] / ev_[1] are recorded behind the census read-back and the tie
+  // word's pass (sort_writables with ms turns them into name_times).
+  int name_order(void* tmp, size_t tmp_bytes, const uint8_t* base, const uint64_t* name_pos, const uint8_t* name_len,
+                 const uint8_t* tie, uint64_t n, uint64_t* word, uint64_t* word2, uint32_t* scratch, uint32_t* perm,
+                 bool timed = false);
+  const uint64_t* name_counters() const { return name_counters_; }
+  // HIP-event milliseconds of the last timed queryname sort_writables: name
+  // references + census + read-back, the tie word's pass, the chunk passes
+  const float* name_times() const { return name_ms_; }
 
   // .splitting-bai entries of a span whose first record has global ordinal
   // `ordinal0` (SplittingBAMIndexer.java:273-277: ordinals k*g - 1)
@@ -469,6 +483,12 @@ class Pipeline {
   DevBuf<uint64_t> sort_word_, sort_word2_, sort_slen_, sort_doff_;
   DevBuf<uint32_t> sort_len_, sort_iota_, sort_perm_;
   DevBuf<uint8_t> sort_tmp_;
+  // queryname order: where each name starts, its length, the tie word; the census words
+  DevBuf<uint64_t> name_pos_, name_census_;
+  DevBuf<uint8_t> name_len_, name_tie_;
+  uint64_t name_counters_[3] = {0, 0, 0};
+  float name_ms_[3] = {0, 0, 0};
+  bool name_full_ = false;  // HBAM_NAME_FULL_PASSES: no chunk skipped, no bit range narrowed (measurement)
 
   hipEvent_t ev_[8];
   std::vector<hipEvent_t> tev_;     // timing events of overlapped inflate chunks

@@ -136,6 +136,7 @@ _sig("hbam_encode_writables", C.c_int, [P, P, u64, P, C.POINTER(u64)])
 _sig("hbam_sort_writables", C.c_int, [P, i32, P, u64, P, P, C.POINTER(u64)])
 _sig("hbam_decode_writables", C.c_int, [P, P, u64, P, u64, C.POINTER(Batch)])
 _sig("hbam_open_codec", C.c_int, [C.POINTER(Opts), C.POINTER(P)])
+_sig("hbam_sort_name_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_merge_begin", C.c_int, [P, i32])
 _sig("hbam_merge_add_run", C.c_int, [P, P, u64, P, u64, P])
 _sig("hbam_merge_plan", C.c_int, [P, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
@@ -144,6 +145,8 @@ _sig("hbam_merge_end", C.c_int, [P])
 _sig("hbam_merge_times", C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_float)])
 _sig("hbam_gpu_encode_writables", C.c_int, [P, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_sort_writables", C.c_int, [P, i32, i32, C.POINTER(C.c_float), C.POINTER(u64)])
+_sig("hbam_gpu_sort_name_counters", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_gpu_sort_name_times", C.c_int, [P, C.POINTER(C.c_float)])
 _sig("hbam_gpu_fetch_encoded", C.c_int, [P, u64, u64, P])
 _sig("hbam_gpu_reload", C.c_int, [P, P, u64, i32, C.POINTER(C.c_float)])
 _sig("hbam_gpu_run_streamed", C.c_int, [P, P, u64, u64, C.POINTER(GpuStats)])
@@ -158,8 +161,8 @@ _sig("hbam_bai_query", C.c_int, [P, u64, P, u64, C.POINTER(P), C.POINTER(u64)])
 
 BGZF_EOF = 1
 LOCATE_SEG_DEFAULT = (1 << 64) - 1  # hbam_set_locate: the built-in segment size
-SORT_KEY, SORT_COORDINATE = 0, 1  # hbam_sort_writables orders
-SORT_ORDERS = {"key": SORT_KEY, "coordinate": SORT_COORDINATE}
+SORT_KEY, SORT_COORDINATE, SORT_QUERYNAME = 0, 1, 3  # hbam_sort_writables orders (2 is not one)
+SORT_ORDERS = {"key": SORT_KEY, "coordinate": SORT_COORDINATE, "queryname": SORT_QUERYNAME}
 BAI_METADATA = 1  # hbam_build_bai: the pseudo-bins 37450 and the trailing n_no_coor
 HTSJDK_BLOCK_SIZE = 65498  # ISIZE of every full block of test.bam (htsjdk-written)
 
@@ -346,7 +349,7 @@ class _Merge:
         array or an np.memmap: not copied, a reference is kept until
         merge_end), offs = n + 1 record starts with offs[n] = len(enc), words
         = its n sort words (hbam.sort.sort_words) or None: computed on the GPU
-        from the encodings."""
+        from the encodings (queryname order has no words: None only)."""
         if isinstance(enc, np.ndarray):
             buf = enc if enc.dtype == np.uint8 and enc.ndim == 1 and enc.flags.c_contiguous else \
                 np.ascontiguousarray(enc).view(np.uint8).reshape(-1)
@@ -389,6 +392,16 @@ class _Merge:
         if rc != OK:
             raise self._merge_err(rc)
         return out.raw[:ln.value], offs, src
+
+    def sort_name_counters(self):
+        """(chunks present, chunks sorted, radix bits sorted) of the last
+        queryname order computed on this ctx, by sort_writables or merge_plan
+        (hbam_sort_name_counters)."""
+        w = (u64 * 3)()
+        rc = _L.hbam_sort_name_counters(self._h, w)
+        if rc != OK:
+            raise self._merge_err(rc)
+        return int(w[0]), int(w[1]), int(w[2])
 
     def merge_end(self):
         if self._h:
@@ -762,9 +775,11 @@ class BamFile(_Merge):
     def sort_writables(self, order="key"):
         """encode_writables with the records sorted on the GPU
         (hbam_sort_writables): order "key" (the shuffle's: ascending signed
-        BAMRecordReader key) or "coordinate" (refID, pos; unplaced last), both
-        stable.  (bytes, offsets[u64, n+1], perm[u32, n]): perm[j] = the batch
-        index of the j-th output record."""
+        BAMRecordReader key), "coordinate" (refID, pos; unplaced last) or
+        "queryname" (the read name as unsigned bytes, then first / second of
+        pair and primary before secondary / supplementary), all stable.
+        (bytes, offsets[u64, n+1], perm[u32, n]): perm[j] = the batch index of
+        the j-th output record."""
         o = SORT_ORDERS.get(order, order)
         n = u64()
         rc = _L.hbam_sort_writables(self._h, o, None, 0, None, None, C.byref(n))
@@ -1077,6 +1092,25 @@ class Gpu:
         if rc != OK:
             raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
         return (ms[0], ms[1], ms[2]), nb.value
+
+    def sort_name_counters(self):
+        """(chunks present, chunks sorted, radix bits sorted) of the last
+        queryname sort_writables (hbam_gpu_sort_name_counters)."""
+        w = (u64 * 3)()
+        rc = _L.hbam_gpu_sort_name_counters(self._h, w)
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        return int(w[0]), int(w[1]), int(w[2])
+
+    def sort_name_times(self):
+        """(ms name references + census + read-back, ms tie pass, ms chunk
+        passes) inside the order step of the last timed queryname
+        sort_writables (hbam_gpu_sort_name_times)."""
+        ms = (C.c_float * 3)()
+        rc = _L.hbam_gpu_sort_name_times(self._h, ms)
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        return ms[0], ms[1], ms[2]
 
     def fetch_encoded(self, pos, length):
         buf = C.create_string_buffer(max(length, 1))

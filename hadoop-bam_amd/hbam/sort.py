@@ -14,7 +14,7 @@ import tempfile
 
 import numpy as np
 
-from . import E_ARG, E_STATE, OK, SORT_ORDERS, STRICT, BamFile, Batch, HbamError, _L
+from . import E_ARG, E_STATE, OK, SORT_ORDERS, STRICT, BamFile, Batch, Codec, HbamError, _L
 from .writer import BamWriter
 
 MERGE_BATCH_RECORDS = 1 << 20  # records per run at most (a run is also cut at its window's end)
@@ -24,8 +24,11 @@ def sort_words(key, ref_id, pos, order):
     """The 64-bit word hbam_sort_writables and hbam_merge_* order records by
     (k_sort_words, restated in NumPy): "key": (uint64)key ^ 1 << 63;
     "coordinate": (uint64)(uint32)refID << 32 | (uint32)(pos + 1).  Ascending
-    unsigned order of the words is the order's."""
+    unsigned order of the words is the order's.  "queryname" has no such word
+    (its key is the read name's bytes): HbamError(E_ARG)."""
     o = SORT_ORDERS.get(order, order)
+    if o == SORT_ORDERS["queryname"]:
+        raise HbamError(E_ARG, "queryname order has no sort word")
     if o == SORT_ORDERS["key"]:
         return np.asarray(key, np.int64).view(np.uint64) ^ np.uint64(1 << 63)
     if o != SORT_ORDERS["coordinate"]:
@@ -35,13 +38,18 @@ def sort_words(key, ref_id, pos, order):
     return (ref << np.uint64(32)) | pos1
 
 
-def sorted_header(header_bytes: bytes) -> bytes:
+def sorted_header(header_bytes: bytes, order="coordinate") -> bytes:
     """The BAM header (magic, l_text, text, references) with SO:coordinate in
     its @HD line: an existing SO: value is replaced, an @HD line without one
     gets "\\tSO:coordinate" appended, a text without an @HD line gets
     "@HD\\tVN:1.5\\tSO:coordinate\\n" in front.  l_text follows; every other
     byte is kept.  The role of util/GetSortedBAMHeader; htsjdk re-serialises
-    the whole header there, and byte equality with that is not claimed."""
+    the whole header there, and byte equality with that is not claimed.
+    order "queryname": SO:queryname by the same three rules (no SS field is
+    written: the collation is hbam_sort_writables', not one SS names)."""
+    if order not in ("coordinate", "queryname"):
+        raise ValueError(f"no SO: value for order {order!r}")
+    so = b"SO:" + order.encode()
     h = bytes(header_bytes)
     if h[:4] != b"BAM\x01":
         raise ValueError("not a BAM header")
@@ -53,12 +61,12 @@ def sorted_header(header_bytes: bytes) -> bytes:
             end = len(text.rstrip(b"\0"))
         fields = text[:end].split(b"\t")
         if any(f.startswith(b"SO:") for f in fields[1:]):
-            fields = [fields[0]] + [b"SO:coordinate" if f.startswith(b"SO:") else f for f in fields[1:]]
+            fields = [fields[0]] + [so if f.startswith(b"SO:") else f for f in fields[1:]]
         else:
-            fields.append(b"SO:coordinate")
+            fields.append(so)
         text = b"\t".join(fields) + text[end:]
     else:
-        text = b"@HD\tVN:1.5\tSO:coordinate\n" + text
+        text = b"@HD\tVN:1.5\t" + so + b"\n" + text
     return h[:4] + len(text).to_bytes(4, "little") + text + rest
 
 
@@ -66,8 +74,10 @@ def sort_bam(src, out, order="coordinate", level=5, splitting_bai=None, granular
              stringency=STRICT, window_bytes=0, merge=False, part_bytes=0, spill_dir=None):
     """Write the BAM `src` (a path or the file's bytes) to `out` (a path or a
     binary file object) with its records sorted on the GPU: order "coordinate"
-    (the header gets SO:coordinate) or "key" (the shuffle's order, header
-    unchanged).  Ties keep the input order.  splitting_bai: a binary file
+    (the header gets SO:coordinate), "queryname" (by read name, then first /
+    second of pair and primary before secondary / supplementary; the header
+    gets SO:queryname) or "key" (the shuffle's order, header unchanged).  Ties
+    keep the input order.  splitting_bai: a binary file
     object that receives the write-time .splitting-bai.  Returns the number of
     records.  Without merge the file must decode as one window of window_bytes
     compressed bytes (0: the library's default).  merge=True: the file is read
@@ -85,8 +95,8 @@ def sort_bam(src, out, order="coordinate", level=5, splitting_bai=None, granular
     f = BamFile(path=os.fspath(src), **kw) if isinstance(src, (str, os.PathLike)) else BamFile(src, **kw)
     try:
         header = f.header_bytes()
-        if order == "coordinate":
-            header = sorted_header(header)
+        if order in ("coordinate", "queryname"):
+            header = sorted_header(header, order)
         # the whole file as one batch, left in the library's columns (nothing copied into Python)
         b = Batch()
         rc = _L.hbam_decode_span(f._h, f.header()["first_record_voff"], (1 << 64) - 1, 0, C.byref(b))
@@ -123,38 +133,47 @@ def _sort_bam_merge(src, out, order, level, splitting_bai, granularity, eof, dev
     spilled = []
     kw = dict(device=device, stringency=stringency, window_bytes=window_bytes)
     f = BamFile(path=os.fspath(src), **kw) if isinstance(src, (str, os.PathLike)) else BamFile(src, **kw)
+    # queryname order has no sort words: merge_add_run decodes each run
+    # (hbam_decode_writables), which would end the split iter_batches is
+    # reading on the file's ctx, so this order's merge runs on a ctx of its own
+    by_name = SORT_ORDERS.get(order, order) == SORT_ORDERS["queryname"]
+    m = f
     try:
+        if by_name:
+            m = Codec(device)
         header = f.header_bytes()
-        if order == "coordinate":
-            header = sorted_header(header)
-        f.merge_begin(order)
+        if order in ("coordinate", "queryname"):
+            header = sorted_header(header, order)
+        m.merge_begin(order)
         total = 0
         for r in f.iter_batches(f.header()["first_record_voff"], (1 << 64) - 1, MERGE_BATCH_RECORDS):
             if r["status"] != OK:
                 raise f._err(r["status"])
             enc, offs, perm = f.sort_writables(order)
-            words = sort_words(r["key"], r["ref_id"], r["pos"], order)[perm]
+            words = None if by_name else sort_words(r["key"], r["ref_id"], r["pos"], order)[perm]
             if spill_dir is not None and len(enc):
                 fd, path = tempfile.mkstemp(prefix="hbam_run_", suffix=".spill", dir=os.fspath(spill_dir))
                 spilled.append(path)
                 with os.fdopen(fd, "wb") as g:
                     g.write(enc)
                 enc = np.memmap(path, np.uint8, "r")
-            f.merge_add_run(enc, offs, words)
+            m.merge_add_run(enc, offs, words)
             total += len(perm)
         if isinstance(out, (str, os.PathLike)):
             out = opened = open(out, "wb")
         w = BamWriter(out, header=header, level=level, splitting_bai=splitting_bai, granularity=granularity,
                       device=device)
-        for enc, offs, _ in f.iter_merged(part_bytes):
+        for enc, offs, _ in m.iter_merged(part_bytes):
             w.write_records(enc, offs)
         w.close(eof=eof)
-        f.merge_end()
+        m.merge_end()
         return total
     finally:
         try:
-            f.merge_end()  # (drops the references to the mapped runs before their files go)
+            m.merge_end()  # (drops the references to the mapped runs before their files go)
         finally:
+            if m is not f:
+                m.close()
             f.close()
             for path in spilled:
                 try:

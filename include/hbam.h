@@ -355,8 +355,31 @@ int hbam_encode_writables(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *o
  *   HBAM_SORT_COORDINATE  ascending (uint64)(uint32)refID << 32 | (uint32)(pos + 1):
  *       contigs in dictionary order, refID -1 last, pos -1 first within its
  *       contig, a placed unmapped read at its position.
- * Both orders are stable: records with equal sort words keep their batch order.
- * That tie order is neither htsjdk's SAMRecordCoordinateComparator (which goes
+ *   HBAM_SORT_QUERYNAME   by read name (SO:queryname; samtools sort -n's and
+ *       Picard SortSam SORT_ORDER=queryname's family).  Record a comes before
+ *       record b when the first of these keys that differs says so:
+ *       1. the name: the min(l_read_name, rest length) bytes at byte 36 of the
+ *          record's encoding, zero-extended without end and compared as unsigned
+ *          bytes, lexicographically (a name that is a prefix of another comes
+ *          first; bytes >= 0x80 sort after ASCII).  For well-formed names
+ *          (printable ASCII, one terminating NUL) this is String.compareTo on
+ *          the read names.  l_read_name 0 (possible under SILENT) is the empty
+ *          name.  No byte outside the record and the source's padding is read.
+ *       2. the tie word t = 2 * m + s from the flag: m = 3 when 0x1 is clear;
+ *          else 0 when exactly 0x40 of {0x40, 0x80} is set, 2 when exactly 0x80
+ *          is set, 1 when both or neither; s = 1 when 0x100 or 0x800 is set,
+ *          else 0.  First of pair before second of pair, paired before unpaired,
+ *          primary before secondary or supplementary.
+ *       3. the batch order (stable).
+ *       The tie word is modelled on the leading rules of htsjdk's
+ *       SAMRecordQueryNameComparator; equality with that comparator (which goes
+ *       on to strand, the HI tag, ...) or with samtools' natural name order is
+ *       NOT claimed: htsjdk was not available to compare against.  The order is
+ *       a valid SO:queryname order under the SAM specification (which leaves the
+ *       collation to the implementation).  There is no 64-bit sort word for
+ *       this order; the value 2 is not an order and is refused.
+ * All orders are stable: records with equal sort words keep their batch order.
+ * For key and coordinate, that tie order is neither htsjdk's SAMRecordCoordinateComparator (which goes
  * on to strand, read name, flags, ...) nor samtools' strand tie-break; it is a
  * valid SO:coordinate order under the SAM specification, and the order
  * hbam_build_bai accepts.
@@ -367,6 +390,7 @@ int hbam_encode_writables(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *o
  * or n >= 2^31 - 1 -> HBAM_E_ARG.  n == 0 -> HBAM_OK with *len = 0. */
 #define HBAM_SORT_KEY        0
 #define HBAM_SORT_COORDINATE 1
+#define HBAM_SORT_QUERYNAME  3
 int hbam_sort_writables(hbam_ctx *ctx, int32_t order, uint8_t *out, uint64_t cap, uint64_t *offs, uint32_t *perm,
                         uint64_t *len);
 /* SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) for n serialized
@@ -378,6 +402,14 @@ int hbam_sort_writables(hbam_ctx *ctx, int32_t order, uint8_t *out, uint64_t cap
  * HBAM_E_FORMAT; framing outside buf -> HBAM_E_ARG. */
 int hbam_decode_writables(hbam_ctx *ctx, const void *buf, uint64_t len, const uint64_t *offs, uint64_t n,
                           hbam_batch *out);
+/* Measurement: what the last HBAM_SORT_QUERYNAME order computed on ctx (an
+ * hbam_sort_writables or an hbam_merge_plan) did.  The order is a radix sort
+ * over the names' 8-byte chunks; a chunk index in which no two names differ is
+ * skipped and the others sort only the bits that differ.  out[0] = the chunks
+ * of the longest name, out[1] = the chunks sorted, out[2] = the radix bits
+ * those sorts covered (the tie word's 3-bit pass is not counted).  Zeros
+ * before the first such order. */
+int hbam_sort_name_counters(hbam_ctx *ctx, uint64_t out[3]);
 /* A ctx with a device and no file, for reducers that only call
  * hbam_decode_writables. */
 int hbam_open_codec(const hbam_opts *opts, hbam_ctx **out);
@@ -394,8 +426,8 @@ int hbam_open_codec(const hbam_opts *opts, hbam_ctx **out);
  * size is not bounded by HBM.  Works on a file ctx or a codec ctx; one merge
  * per ctx at a time.  The ctx serves every other call meanwhile.
  *
- * hbam_merge_begin: order = HBAM_SORT_KEY / HBAM_SORT_COORDINATE; another value
- * -> HBAM_E_ARG; a merge already open on ctx -> HBAM_E_STATE.
+ * hbam_merge_begin: order = HBAM_SORT_KEY / HBAM_SORT_COORDINATE /
+ * HBAM_SORT_QUERYNAME; another value -> HBAM_E_ARG; a merge already open on ctx -> HBAM_E_STATE.
  *
  * hbam_merge_add_run: run = buf[0, len), record i = buf[offs[i], offs[i+1])
  * (offs: n + 1 entries, offs[n] == len).  buf and offs stay the caller's and
@@ -407,6 +439,11 @@ int hbam_open_codec(const hbam_opts *opts, hbam_ctx **out);
  * the run, whose errors apply to a bad value; the ctx's last batch becomes that
  * decode's).  With words given the last batch is untouched: a file ctx can
  * alternate hbam_decode_span, hbam_sort_writables and hbam_merge_add_run.
+ * HBAM_SORT_QUERYNAME has no sort word: words must be NULL (else HBAM_E_ARG,
+ * "words" in the message), the run is decoded as above, its records' names are
+ * copied into HBM (name bytes + 10 B per record, held until hbam_merge_end) and
+ * checked to be in (name, tie word) order.  The decode ends a split being read
+ * with hbam_decode_span on the same ctx: merge on a codec ctx beside it.
  * Checked on the GPU, HBAM_E_ARG: offsets that do not increase, a record
  * shorter than 36 bytes or ending past len, offs[n] != len, words that are not
  * non-decreasing (hbam_last_error names the run and the first offending
@@ -597,6 +634,15 @@ int hbam_gpu_set_stringency(hbam_gpu *g, int32_t stringency);
 /* hbam_set_locate / hbam_locate_counters of the loaded file's pipeline */
 int hbam_gpu_set_locate(hbam_gpu *g, uint64_t seg_bytes, uint32_t cap_limit);
 int hbam_gpu_locate_counters(hbam_gpu *g, uint64_t out[2]);
+/* hbam_sort_name_counters of the loaded file's pipeline */
+int hbam_gpu_sort_name_counters(hbam_gpu *g, uint64_t out[3]);
+/* Measurement: HIP-event milliseconds inside the order step (ms[0] of
+ * hbam_gpu_sort_writables) of the last round of the last HBAM_SORT_QUERYNAME
+ * call: name references + census + its read-back, the tie word's pass, the
+ * chunk passes.  With HBAM_NAME_FULL_PASSES=1 in the environment when the file
+ * is loaded, every chunk present is sorted over all 64 bits (the A/B of the
+ * census's skipping and narrowing; the order is the same). */
+int hbam_gpu_sort_name_times(hbam_gpu *g, float ms[3]);
 /* One pass of the hot path over the resident file, first record to EOF:
  * BGZF discovery, inflate, record scan, field decode + keys + voffs, window by
  * window (flags as hbam_decode_span_device). */

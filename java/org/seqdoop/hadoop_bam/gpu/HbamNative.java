@@ -204,10 +204,20 @@ public final class HbamNative {
 
   /** {@link #sortWritables} orders: the shuffle's (signed key) / (refID, pos) with unplaced reads last. */
   public static final int SORT_KEY = 0, SORT_COORDINATE = 1;
+  /**
+   * {@link #sortWritables} order by read name (SO:queryname): the name's bytes
+   * compared unsigned (String.compareTo for well-formed names), then first
+   * before second of pair, paired before unpaired, primary before secondary or
+   * supplementary, then batch order.  Modelled on the leading rules of htsjdk's
+   * SAMRecordQueryNameComparator; equality with it is not claimed.  (2 is not an
+   * order.)
+   */
+  public static final int SORT_QUERYNAME = 3;
 
   /**
    * hbam_sort_writables: encodeWritables with the records of the last decodeSpan
-   * sorted on the GPU (stable; order SORT_KEY or SORT_COORDINATE).  offs (n + 1)
+   * sorted on the GPU (stable; order SORT_KEY, SORT_COORDINATE or
+   * SORT_QUERYNAME).  offs (n + 1)
    * receives the output starts, perm (n) the batch index of each output record;
    * either may be null.  Returns the total (out == null only sizes).
    */
@@ -217,7 +227,11 @@ public final class HbamNative {
   /**
    * hbam_merge_begin: open the merge of sorted runs on ctx (a file or a codec
    * context) -- the reduce side of the sort job, Hadoop's merge of the sorted
-   * map outputs.  order: SORT_KEY or SORT_COORDINATE.
+   * map outputs.  order: SORT_KEY, SORT_COORDINATE or SORT_QUERYNAME.  In
+   * SORT_QUERYNAME there are no sort words: mergeAddRun takes words == null
+   * (IllegalArgumentException otherwise), decodes the run and keeps its names in
+   * HBM; as that decode ends a split being read on the same context, merge on a
+   * codec context.
    */
   public static native void mergeBegin(long ctx, int order) throws IOException;
 

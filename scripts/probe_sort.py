@@ -9,14 +9,22 @@ times, alternating, `reps` rounds of `iters` launches each (HIP events inside
 the library):
   * hbam_gpu_encode_writables: the in-order copy of the same bytes, the roof
     of the gather;
-  * hbam_gpu_sort_writables for both orders: sort words + radix sort, lengths +
-    scan, gather;
+  * hbam_gpu_sort_writables for the key, coordinate and queryname orders: the
+    order (sort words + radix sort; for queryname the name references, the
+    census and its read-back, the tie word's pass and the chunk passes, also
+    split: hbam_gpu_sort_name_times), lengths + scan, gather;
+  * the queryname order once more on a second session of the same file loaded
+    with HBAM_NAME_FULL_PASSES=1: every chunk present sorted over all 64 bits,
+    the A/B of the census's skipping and narrowing;
 and once hbam_gpu_d2d_bandwidth.  Last, the host path a user has without the
 feature, `reps` times with a host clock: hbam_decode_span of the whole file
 (decode + the batch's D2H; hbam_decode_span_device beside it is the decode
 alone), NumPy's stable argsort of the keys, and a byte gather on the host
 (bytes.join over the records' rests as the batch delivers them; rebuilding the
-36-byte heads from the columns would come on top).
+36-byte heads from the columns would come on top); and for the queryname order
+the names sliced out of the batch's rests and ordered by Python's sorted() and
+by NumPy's stable argsort of a fixed-width bytes array (the names alone: no tie
+word).
 
 Every GPU step runs under a time limit of its own: a step that overruns ends
 the process (a traceback on stderr, exit status 1) before anything else is
@@ -89,17 +97,29 @@ def main():
     out = {"records": a.records, "record_bytes": nbytes, "compressed_bytes": len(data), "reps": a.reps,
            "iters": a.iters}
 
-    enc_ms, stages = [], {o: ([], [], []) for o in ("key", "coordinate")}
+    enc_ms, stages = [], {o: ([], [], []) for o in ("key", "coordinate", "queryname")}
+    name_ms, full_ms, full_name_ms = ([], [], []), ([], [], []), ([], [], [])
     g = hbam.Gpu(a.device)
+    g_full = hbam.Gpu(a.device)  # the same file, every name chunk sorted over 64 bits
     try:
-        g.set_stringency(hbam.SILENT)
-        with limit(120, "load + decode"):
-            g.load(data)
-            assert g.run()["records"] == a.records
+        for s, full in ((g, "0"), (g_full, "1")):
+            s.set_stringency(hbam.SILENT)
+            with limit(120, "load + decode"):
+                os.environ["HBAM_NAME_FULL_PASSES"] = full  # read when the session's pipeline is made
+                s.load(data)
+                assert s.run()["records"] == a.records
+        del os.environ["HBAM_NAME_FULL_PASSES"]
         with limit(60, "warm-up"):
             g.encode_writables(iters=1)
             for order in stages:
                 g.sort_writables(order, iters=1)
+            g_full.encode_writables(iters=1)
+            g_full.sort_writables("queryname", iters=1)
+        out["queryname_counters"] = dict(zip(("chunks_present", "chunks_sorted", "bits_sorted"),
+                                             g.sort_name_counters()))
+        out["queryname_full_counters"] = dict(zip(("chunks_present", "chunks_sorted", "bits_sorted"),
+                                                  g_full.sort_name_counters()))
+        assert g.fetch_encoded(0, nbytes) == g_full.fetch_encoded(0, nbytes)  # the same order either way
         for rep in range(a.reps):
             with limit(60, f"round {rep}"):
                 ms, nb = g.encode_writables(iters=a.iters)
@@ -110,10 +130,19 @@ def main():
                     assert nb == nbytes
                     for k in range(3):
                         lists[k].append(t[k])
+                    if order == "queryname":  # (the split of the round's last launch)
+                        for k, v in enumerate(g.sort_name_times()):
+                            name_ms[k].append(v)
+                t, nb = g_full.sort_writables("queryname", iters=a.iters)
+                for k in range(3):
+                    full_ms[k].append(t[k])
+                for k, v in enumerate(g_full.sort_name_times()):
+                    full_name_ms[k].append(v)
         with limit(60, "device-to-device copy bandwidth"):
             out["d2d_gbps"] = round(g.d2d_bandwidth(1 << 30, 5), 1)
     finally:
         g.close()
+        g_full.close()
     out["encode_in_order_ms"] = spread(enc_ms)
     enc = statistics.median(enc_ms)
     out["encode_in_order_gbps"] = round(2 * nbytes / enc / 1e6, 1)  # read + write
@@ -122,8 +151,13 @@ def main():
         out[order] = {"sort_ms": spread(s), "offsets_ms": spread(l), "gather_ms": spread(gth),
                       "total_ms": spread([x + y + z for x, y, z in zip(s, l, gth)]),
                       "gather_gbps": round(2 * nbytes / med / 1e6, 1), "gather_over_in_order_copy": round(med / enc, 3)}
+    split = ("refs_census_readback_ms", "tie_pass_ms", "chunk_passes_ms")
+    out["queryname"].update({k: spread(v) for k, v in zip(split, name_ms)})
+    out["queryname_full_passes"] = {"sort_ms": spread(full_ms[0]), "offsets_ms": spread(full_ms[1]),
+                                    "gather_ms": spread(full_ms[2])}
+    out["queryname_full_passes"].update({k: spread(v) for k, v in zip(split, full_name_ms)})
 
-    t_dev, t_d2h, t_arg, t_gather = [], [], [], []
+    t_dev, t_d2h, t_arg, t_gather, t_names, t_sorted, t_np = [], [], [], [], [], [], []
     with hbam.BamFile(data, device=a.device, stringency=hbam.SILENT) as f:
         first = f.header()["first_record_voff"]
         for rep in range(a.reps + 1):  # rep 0 warms up
@@ -146,6 +180,20 @@ def main():
             gathered = b"".join(raw[rest_off[i]:hi[i]] for i in order)
             t5 = time.perf_counter()
             assert len(gathered) == nbytes - 36 * a.records
+            lrn = np.ctypeslib.as_array((C.c_uint8 * b.n).from_address(b.l_read_name)).astype(np.int64)
+            t6 = time.perf_counter()
+            ends = (rest_off + np.minimum(lrn, rest_len)).tolist()
+            names = [bytes(raw[x:y]) for x, y in zip(rest_off.tolist(), ends)]
+            t7 = time.perf_counter()
+            by_name = sorted(range(b.n), key=names.__getitem__)
+            t8 = time.perf_counter()
+            by_name_np = np.argsort(np.array(names, dtype=np.bytes_), kind="stable")
+            t9 = time.perf_counter()
+            assert len(by_name) == len(by_name_np) == b.n
+            if rep:
+                t_names.append((t7 - t6) * 1e3)
+                t_sorted.append((t8 - t7) * 1e3)
+                t_np.append((t9 - t8) * 1e3)
             if rep:
                 t_dev.append((t1 - t0) * 1e3)
                 t_d2h.append((t2 - t1) * 1e3)
@@ -153,6 +201,8 @@ def main():
                 t_gather.append((t5 - t4) * 1e3)
     out["host_path"] = {"decode_device_ms": spread(t_dev), "decode_span_with_d2h_ms": spread(t_d2h),
                         "numpy_argsort_ms": spread(t_arg), "host_gather_ms": spread(t_gather),
+                        "name_slices_ms": spread(t_names), "python_sorted_names_ms": spread(t_sorted),
+                        "numpy_argsort_names_ms": spread(t_np),
                         "host_gather": "bytes.join over the records' rests as the batch delivers them "
                                        "(the 36-byte heads are not rebuilt)"}
     print(json.dumps(out))
