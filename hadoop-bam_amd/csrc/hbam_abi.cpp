@@ -43,6 +43,7 @@ struct hbam_ctx {
   bool last_is_writables = false;
   std::unique_ptr<QueryCursor> query;  // the open bounded traversal (hbam_query_*), if any
   bool last_is_query = false;          // the last batch came from hbam_query_next
+  bool has_span_batch = false;         // an hbam_decode_span batch is the ctx's last (hbam_format_sam asks)
   std::unique_ptr<hbam::Merger> merge;  // the open merge (hbam_merge_*), if any (destroyed first: its buffers
                                         // wait for the pipeline's streams)
 };
@@ -50,6 +51,7 @@ struct hbam_ctx {
 // Forget the split and the query being read: the call about to run moves the
 // ctx's window.
 static void reset_cursors(hbam_ctx* ctx) {
+  ctx->has_span_batch = false;
   ctx->cursor.reset();
   ctx->query.reset();
 }
@@ -414,6 +416,7 @@ int hbam_decode_span(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, uint64_t max
   ctx->last_is_writables = false;
   ctx->last_is_query = false;
   ctx->query.reset();  // a split read ends an open query
+  ctx->has_span_batch = true;
   uint64_t next = vend;
   int rc = ctx->cursor.next_batch(*ctx->f, vstart, vend, max_records, &ctx->batch, &next, &ctx->err);
   fill_batch(ctx->batch, out);
@@ -593,6 +596,65 @@ int hbam_encode_writables(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* o
     return HBAM_E_DEVICE;
   }
   rc = p.encode_writables(span, bytes, dst.p);
+  if (rc != HBAM_OK) {
+    ctx->err = p.error();
+    return rc;
+  }
+  if (hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, p.stream()) != hipSuccess ||
+      hipStreamSynchronize(p.stream()) != hipSuccess) {
+    ctx->err = "hipMemcpy D2H failed";
+    return HBAM_E_DEVICE;
+  }
+  return HBAM_OK;
+}
+
+int hbam_format_sam(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, uint64_t* len) {
+  *len = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  hbam::Pipeline& p = ctx->f->pipe();
+  hbam::SpanDev span;
+  if (!ctx->has_span_batch || ctx->last_is_writables || ctx->last_is_query ||
+      (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
+    ctx->err = "hbam_format_sam needs a one-window batch from hbam_decode_span";
+    return HBAM_E_STATE;
+  }
+  const uint64_t n = ctx->batch.n;
+  if (n == 0) {
+    if (offs) offs[0] = 0;
+    return HBAM_OK;
+  }
+  if (n >= 0x7fffffffull) {
+    ctx->err = "too many records to format in one batch";
+    return HBAM_E_ARG;
+  }
+  uint64_t bytes = 0, bad = ~0ull;
+  int rc = p.set_sam_refs(ctx->f->ref_names());
+  if (rc == HBAM_OK) rc = p.sam_measure(span, &bytes, &bad);
+  if (rc != HBAM_OK) {
+    ctx->err = p.error();
+    return rc;
+  }
+  if (bad != ~0ull) {
+    ctx->err = "malformed aux fields in record " + std::to_string(bad) + " of the batch";
+    return HBAM_E_FORMAT;
+  }
+  *len = bytes;
+  if (offs && (hipMemcpyAsync(offs, p.sam_offsets(), (n + 1) * 8, hipMemcpyDeviceToHost, p.stream()) != hipSuccess ||
+               hipStreamSynchronize(p.stream()) != hipSuccess)) {
+    ctx->err = "hipMemcpy D2H failed";
+    return HBAM_E_DEVICE;
+  }
+  if (!out) return HBAM_OK;
+  if (cap < bytes) {
+    ctx->err = "output buffer too small for the SAM text";
+    return HBAM_E_ARG;
+  }
+  hbam::DevBuf<uint8_t> dst(&p.streams());
+  if (dst.reserve((bytes + 15) & ~15ull) != hipSuccess) {
+    ctx->err = "device allocation of the SAM text failed";
+    return HBAM_E_NOMEM;
+  }
+  rc = p.sam_write(span, bytes, dst.p);
   if (rc != HBAM_OK) {
     ctx->err = p.error();
     return rc;
@@ -1291,6 +1353,43 @@ int hbam_gpu_sort_writables(hbam_gpu* g, int32_t order, int32_t iters, float ms[
   for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) {
     float t[3];
     rc = p.sort_writables(g->span, order, nb, g->enc.p, t);
+    for (int k = 0; k < 3; ++k) ms[k] += t[k] / (float)iters;
+  }
+  if (rc == HBAM_OK && hipStreamSynchronize(p.stream()) != hipSuccess) {
+    g->err = "hipStreamSynchronize failed";
+    return HBAM_E_DEVICE;
+  }
+  if (rc != HBAM_OK) {
+    g->err = p.error();
+    return rc;
+  }
+  g->enc_bytes = nb;
+  *bytes = nb;
+  return HBAM_OK;
+}
+
+int hbam_gpu_format_sam(hbam_gpu* g, int32_t iters, float ms[3], uint64_t* bytes) {
+  ms[0] = ms[1] = ms[2] = 0;
+  *bytes = 0;
+  if (!g->f) return HBAM_E_STATE;
+  hbam::Pipeline& p = g->f->pipe();
+  g->enc.owner = &p.streams();
+  uint64_t nb = 0, bad = ~0ull;
+  int rc = p.set_sam_refs(g->f->ref_names());
+  if (rc == HBAM_OK) rc = p.sam_measure(g->span, &nb, &bad);  // warm-up: sizes the text
+  if (rc == HBAM_OK && bad != ~0ull) {
+    g->err = "malformed aux fields in record " + std::to_string(bad) + " of the window";
+    return HBAM_E_FORMAT;
+  }
+  if (rc == HBAM_OK && g->enc.reserve((nb + 15) & ~15ull) != hipSuccess) {
+    g->err = "device allocation of the SAM text failed";
+    return HBAM_E_NOMEM;
+  }
+  if (rc == HBAM_OK) rc = p.sam_write(g->span, nb, g->enc.p);
+  for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) {
+    float t[3] = {0, 0, 0};
+    rc = p.sam_measure(g->span, &nb, &bad, t);
+    if (rc == HBAM_OK) rc = p.sam_write(g->span, nb, g->enc.p, t + 2);
     for (int k = 0; k < 3; ++k) ms[k] += t[k] / (float)iters;
   }
   if (rc == HBAM_OK && hipStreamSynchronize(p.stream()) != hipSuccess) {

@@ -185,6 +185,26 @@ hipError_t launch_sort_gather(const uint8_t* u, const uint64_t* rec_pos, const i
 // k_sort_words alone: the sort words, encoded lengths and iota of n decoded records
 hipError_t launch_sort_words(const Columns& col, uint64_t n, int order, uint64_t* word, uint32_t* len, uint32_t* iota,
                              hipStream_t s);
+// SAM text of a span's records (hbam_samtext.hip), n < 2^31 - 1: one line per
+// record in batch order.  The reference names: ref_bytes back to back, name r =
+// [ref_off[r], ref_off[r + 1]) (n_ref + 1 u32).
+// temporary storage of the scan over n + 1 lengths
+hipError_t sam_tmp_bytes(uint64_t n, size_t* bytes);
+// head_len[i] = the bytes of line i up to and with the tab behind TLEN, llen[i]
+// = the line's bytes (llen: n + 1 u64, the last 0); *bad (preset ~0) = the first
+// record whose fields do not fit its rest or whose aux fields are malformed
+hipError_t launch_sam_measure(const uint8_t* u, const uint64_t* rec_pos, const Columns& col, uint64_t n,
+                              const uint32_t* ref_off, const uint8_t* ref_bytes, int32_t n_ref, uint32_t* head_len,
+                              uint64_t* llen, unsigned long long* bad, hipStream_t s);
+// doff = the exclusive sum of llen over n + 1 entries: the line starts, doff[n] = the text's bytes
+hipError_t launch_sam_offsets(void* tmp, size_t tmp_bytes, const uint64_t* llen, uint64_t n, uint64_t* doff,
+                              hipStream_t s);
+// dst[doff[i], doff[i + 1]) = line i; total = doff[n]; dst is 16 B-aligned.  Only
+// after a launch_sam_measure of the same records that left *bad = ~0.
+hipError_t launch_sam_write(const uint8_t* u, const uint64_t* rec_pos, const Columns& col, uint64_t n,
+                            const uint32_t* ref_off, const uint8_t* ref_bytes, int32_t n_ref,
+                            const uint32_t* head_len, const uint64_t* doff, uint64_t total, uint8_t* dst,
+                            hipStream_t s);
 // Queryname order (hbam_names.hip): the name = name_len bytes at base +
 // name_pos, zero-extended and compared as unsigned bytes, then the tie word
 // (2 * mate rank + secondary/supplementary, from the flag), then the input

@@ -1433,6 +1433,87 @@ int Pipeline::sort_writables(const SpanDev& s, int order, uint64_t bytes, uint8_
   return kOk;
 }
 
+// a device allocation of the SAM text path: its failure is kErrNoMem
+#define SAMALLOC(expr)                                                        \
+  do {                                                                        \
+    if ((expr) != hipSuccess) return fail(kErrNoMem, "device allocation failed: " #expr); \
+  } while (0)
+
+int Pipeline::set_sam_refs(const std::vector<std::string>& names) {
+  if (sam_n_ref_ >= 0) return kOk;
+  HIPCHK(hipSetDevice(device_));
+  std::vector<uint32_t> off(names.size() + 1, 0);
+  std::string bytes;
+  for (size_t i = 0; i < names.size(); ++i) {
+    bytes += names[i];
+    if (bytes.size() > 0xffffffffull) return fail(kErrArg, "reference names longer than 4 GiB");
+    off[i + 1] = (uint32_t)bytes.size();
+  }
+  own(sam_ref_off_, sam_ref_bytes_, sam_head_, sam_tmp_, sam_llen_, sam_doff_, sam_bad_);
+  SAMALLOC(sam_ref_off_.reserve(off.size()));
+  SAMALLOC(sam_ref_bytes_.reserve(bytes.size() + 1));
+  HIPCHK(hipMemcpyAsync(sam_ref_off_.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, stream_));
+  if (!bytes.empty())
+    HIPCHK(hipMemcpyAsync(sam_ref_bytes_.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, stream_));
+  HIPCHK(hipStreamSynchronize(stream_));  // (the host vectors go away)
+  sam_n_ref_ = (int32_t)names.size();
+  return kOk;
+}
+
+int Pipeline::sam_measure(const SpanDev& s, uint64_t* bytes, uint64_t* bad, float* ms2) {
+  *bytes = 0;
+  *bad = ~0ull;
+  if (ms2) ms2[0] = ms2[1] = 0;
+  if (s.n == 0) return kOk;
+  if (!s.col.ref_id || !s.col.rest_len) return fail(kErrState, "span was not decoded in reader mode");
+  if (sam_n_ref_ < 0) return fail(kErrState, "no reference names set");
+  if (s.n >= 0x7fffffffull) return fail(kErrArg, "too many records to format in one batch");
+  HIPCHK(hipSetDevice(device_));
+  const uint64_t n = s.n;
+  size_t tmp = 0;
+  HIPCHK(sam_tmp_bytes(n, &tmp));
+  SAMALLOC(sam_tmp_.reserve(tmp));
+  SAMALLOC(sam_head_.reserve(n));
+  SAMALLOC(sam_llen_.reserve(n + 1));
+  SAMALLOC(sam_doff_.reserve(n + 1));
+  SAMALLOC(sam_bad_.reserve(1));
+  const uint8_t* src = s.data ? s.data : du_.p;
+  HIPCHK(hipMemsetAsync(sam_bad_.p, 0xff, sizeof(unsigned long long), stream_));
+  if (ms2) HIPCHK(hipEventRecord(ev_[4], stream_));
+  HIPCHK(launch_sam_measure(src, s.rec_pos, s.col, n, sam_ref_off_.p, sam_ref_bytes_.p, sam_n_ref_, sam_head_.p,
+                            sam_llen_.p, sam_bad_.p, stream_));
+  if (ms2) HIPCHK(hipEventRecord(ev_[5], stream_));
+  HIPCHK(launch_sam_offsets(sam_tmp_.p, tmp, sam_llen_.p, n, sam_doff_.p, stream_));
+  if (ms2) HIPCHK(hipEventRecord(ev_[6], stream_));
+  unsigned long long b = ~0ull;
+  HIPCHK(rb(&b, sam_bad_.p, sizeof b, stream_));
+  HIPCHK(rb(bytes, sam_doff_.p + n, 8, stream_));
+  HIPCHK(rb_sync(stream_));
+  *bad = b;
+  if (ms2) {
+    HIPCHK(hipEventElapsedTime(&ms2[0], ev_[4], ev_[5]));
+    HIPCHK(hipEventElapsedTime(&ms2[1], ev_[5], ev_[6]));
+  }
+  return kOk;
+}
+
+int Pipeline::sam_write(const SpanDev& s, uint64_t bytes, uint8_t* dst, float* ms1) {
+  if (ms1) *ms1 = 0;
+  if (s.n == 0 || bytes == 0) return kOk;
+  if (!s.col.ref_id || sam_n_ref_ < 0) return fail(kErrState, "span was not measured");
+  HIPCHK(hipSetDevice(device_));
+  const uint8_t* src = s.data ? s.data : du_.p;
+  if (ms1) HIPCHK(hipEventRecord(ev_[6], stream_));
+  HIPCHK(launch_sam_write(src, s.rec_pos, s.col, s.n, sam_ref_off_.p, sam_ref_bytes_.p, sam_n_ref_, sam_head_.p,
+                          sam_doff_.p, bytes, dst, stream_));
+  if (ms1) {
+    HIPCHK(hipEventRecord(ev_[7], stream_));
+    HIPCHK(hipEventSynchronize(ev_[7]));
+    HIPCHK(hipEventElapsedTime(ms1, ev_[6], ev_[7]));
+  }
+  return kOk;
+}
+
 namespace {
 hipError_t name_readback(void* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
   Pipeline* p = static_cast<Pipeline*>(ctx);

@@ -296,6 +296,21 @@ class Pipeline {
   // order kSortQueryname: the read name, then the flag's tie word (hbam_names.hip)
   const uint32_t* sort_perm() const { return sort_perm_.p; }
   const uint64_t* sort_offsets() const { return sort_doff_.p; }
+  // SAM text of a decoded reader span (hbam_samtext.hip), one line per record
+  // in batch order.  set_sam_refs: the reference names of the file's binary
+  // dictionary, uploaded once as a packed table.  sam_measure: the measure pass
+  // and the scan; *bytes = the text's size, *bad = the span index of the first
+  // record whose fields leave its rest or whose aux fields are malformed (~0:
+  // none; *bytes is then meaningless); the line starts stay on the device
+  // until the next call: sam_offsets() (n + 1 u64, the last = *bytes).
+  // sam_write: the text to dst (device, 16 B-aligned, room for bytes), only
+  // after a sam_measure of the same span that found nothing malformed.  ms
+  // (optional): HIP-event times of (measure, scan) and of the write pass (each
+  // waits for the stream).  A failed device allocation: kErrNoMem.
+  int set_sam_refs(const std::vector<std::string>& names);
+  int sam_measure(const SpanDev& span, uint64_t* bytes, uint64_t* bad, float* ms2 = nullptr);
+  int sam_write(const SpanDev& span, uint64_t bytes, uint8_t* dst, float* ms1 = nullptr);
+  const uint64_t* sam_offsets() const { return sam_doff_.p; }
   // SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) of n values
   // framed by offs in host memory (value i = buf[offs[i], offs[i+1]), the
   // last ends at len): SoA columns + keys; out->n stops at the first bad value.
@@ -490,6 +505,12 @@ class Pipeline {
   float name_ms_[3] = {0, 0, 0};
   bool name_full_ = false;  // HBAM_NAME_FULL_PASSES: no chunk skipped, no bit range narrowed (measurement)
 
+  // SAM text: the reference-name table; head lengths, line lengths, line starts, the malformed flag
+  DevBuf<uint32_t> sam_ref_off_, sam_head_;
+  DevBuf<uint8_t> sam_ref_bytes_, sam_tmp_;
+  DevBuf<uint64_t> sam_llen_, sam_doff_;
+  DevBuf<unsigned long long> sam_bad_;
+  int32_t sam_n_ref_ = -1;  // -1: no table uploaded yet
   hipEvent_t ev_[8];
   std::vector<hipEvent_t> tev_;     // timing events of overlapped inflate chunks
 

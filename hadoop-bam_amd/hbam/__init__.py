@@ -134,6 +134,7 @@ _sig("hbam_gpu_run", C.c_int, [P, i32, C.POINTER(GpuStats)])
 _sig("hbam_gpu_fetch", C.c_int, [P, P, P, u64])
 _sig("hbam_encode_writables", C.c_int, [P, P, u64, P, C.POINTER(u64)])
 _sig("hbam_sort_writables", C.c_int, [P, i32, P, u64, P, P, C.POINTER(u64)])
+_sig("hbam_format_sam", C.c_int, [P, P, u64, P, C.POINTER(u64)])
 _sig("hbam_decode_writables", C.c_int, [P, P, u64, P, u64, C.POINTER(Batch)])
 _sig("hbam_open_codec", C.c_int, [C.POINTER(Opts), C.POINTER(P)])
 _sig("hbam_sort_name_counters", C.c_int, [P, C.POINTER(u64)])
@@ -145,6 +146,7 @@ _sig("hbam_merge_end", C.c_int, [P])
 _sig("hbam_merge_times", C.c_int, [P, C.POINTER(C.c_float), C.POINTER(C.c_float)])
 _sig("hbam_gpu_encode_writables", C.c_int, [P, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_sort_writables", C.c_int, [P, i32, i32, C.POINTER(C.c_float), C.POINTER(u64)])
+_sig("hbam_gpu_format_sam", C.c_int, [P, i32, C.POINTER(C.c_float), C.POINTER(u64)])
 _sig("hbam_gpu_sort_name_counters", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_gpu_sort_name_times", C.c_int, [P, C.POINTER(C.c_float)])
 _sig("hbam_gpu_fetch_encoded", C.c_int, [P, u64, u64, P])
@@ -795,6 +797,22 @@ class BamFile(_Merge):
             raise self._err(rc)
         return out.raw[:total], offs, perm
 
+    def format_sam(self):
+        """The SAM text of every record of the last decode_span, one line per
+        record, formatted on the GPU (hbam_format_sam; float tags print as C's
+        %g): (bytes, offsets[u64, n+1]), offsets[n] = len(bytes)."""
+        n = u64()
+        offs = np.zeros(self._last_n + 1, np.uint64)
+        rc = _L.hbam_format_sam(self._h, None, 0, offs.ctypes.data, C.byref(n))
+        if rc != OK:
+            raise self._err(rc)
+        total = n.value
+        out = C.create_string_buffer(max(total, 1))
+        rc = _L.hbam_format_sam(self._h, out, total, offs.ctypes.data, C.byref(n))
+        if rc != OK:
+            raise self._err(rc)
+        return out.raw[:total], offs
+
     def decode_writables(self, buf: bytes, offs, raise_on_error=True):
         return _decode_writables(self._h, buf, offs, raise_on_error)
 
@@ -1089,6 +1107,17 @@ class Gpu:
         ms = (C.c_float * 3)()
         nb = u64()
         rc = _L.hbam_gpu_sort_writables(self._h, SORT_ORDERS.get(order, order), iters, ms, C.byref(nb))
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        return (ms[0], ms[1], ms[2]), nb.value
+
+    def format_sam(self, iters=10):
+        """hbam_gpu_format_sam of the last run's records into the device
+        buffer fetch_encoded reads, timed over `iters` rounds: ((ms measure,
+        ms scan, ms write) per round, bytes of text)."""
+        ms = (C.c_float * 3)()
+        nb = u64()
+        rc = _L.hbam_gpu_format_sam(self._h, iters, ms, C.byref(nb))
         if rc != OK:
             raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
         return (ms[0], ms[1], ms[2]), nb.value

@@ -393,6 +393,64 @@ int hbam_encode_writables(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *o
 #define HBAM_SORT_QUERYNAME  3
 int hbam_sort_writables(hbam_ctx *ctx, int32_t order, uint8_t *out, uint64_t cap, uint64_t *offs, uint32_t *perm,
                         uint64_t *len);
+/* ---- SAM text ---- */
+/* SAMRecordWriter / [htsjdk] SAMTextWriter.writeAlignment (the text output of
+ * AnySAMOutputFormat, KeyIgnoringSAMRecordWriter; `samtools view`) of every
+ * record of the last hbam_decode_span batch on ctx, formatted on the GPU: one
+ * line per record in batch order, the fields joined by '\t', the line ended by
+ * '\n' (SAM specification 1.4 / 1.5).  No header text is written.
+ *    1 QNAME  the l_read_name - 1 bytes at byte 36 of the record's encoding,
+ *             verbatim; l_read_name <= 1 -> "*"
+ *    2 FLAG   flag, unsigned decimal
+ *    3 RNAME  ref_id == -1 -> "*", else the name of reference ref_id of the
+ *             ctx's binary dictionary (hbam_ref), verbatim
+ *    4 POS    pos + 1 (as a 32-bit sum), signed decimal
+ *    5 MAPQ   mapq, decimal
+ *    6 CIGAR  n_cigar == 0 -> "*", else for each u32 v: v >> 4 in decimal, then
+ *             "MIDNSHP=X"[v & 15]; an op above 8 prints "?".  The CG:B:I
+ *             long-CIGAR convention is not applied: the CIGAR prints as stored.
+ *    7 RNEXT  next_ref_id == -1 -> "*"; == ref_id -> "="; else the reference name
+ *    8 PNEXT  next_pos + 1, as POS
+ *    9 TLEN   tlen, signed decimal
+ *   10 SEQ    l_seq == 0 -> "*", else "=ACMGRSVTWYHKDBN"[nibble], high nibble first
+ *   11 QUAL   l_seq == 0 or the first quality byte 0xFF -> "*", else each byte
+ *             (q + 33) & 0xFF
+ *   12+ aux   in stored order, each as "\tTG:t:value" (a tab before every tag,
+ *             none behind the last):
+ *             A            "A:" and the byte
+ *             c C s S i I  "i:" and the decimal value (C, S, I unsigned)
+ *             f            "f:" and the float (below)
+ *             Z, H         "Z:" / "H:" and the bytes up to the NUL
+ *             B            "B:", the subtype letter (c C s S i I f), then ",value"
+ *                          for each element; a count of 0 prints only "B:c"
+ * Floats: a 32-bit float prints as C's printf("%g") of its value in the "C"
+ * locale: 6 significant digits correctly rounded from the exact binary value
+ * (ties to even), trailing zeros dropped, exponent form below 1e-4 and from
+ * 1e6 on; NaN is "nan", the infinities "inf" and "-inf", negative zero "-0".
+ * This is samtools' text.  htsjdk prints Java's Float.toString: equality with
+ * SAMTextWriter is NOT claimed for float tags (htsjdk was not available to
+ * compare against); every other field follows the SAM specification, which
+ * both writers implement.
+ * *len receives the text's size; out == NULL only sizes (the measuring pass
+ * still runs on the GPU, and offs is filled).  offs (NULL or n + 1 entries)
+ * receives each line's start, offs[n] = *len.  cap < *len with out set ->
+ * HBAM_E_ARG.  n == 0 -> HBAM_OK with *len = 0.
+ * HBAM_E_FORMAT, with the batch index of the first such record in
+ * hbam_last_error and the content of out unspecified: a record whose aux
+ * fields are malformed -- an unknown type byte ('d' included), a Z or H with no
+ * NUL before the record's end, a B with an unknown subtype, a B whose elements
+ * run past the end, a tag header cut by the end -- or, possible under
+ * HBAM_SILENT only, whose read name, CIGAR, bases and qualities do not fit its
+ * rest (or l_seq < 0).  No kernel reads past a record's rest: every step of the
+ * aux walk is bounded by the record's end, in the measuring pass too.
+ * A ref_id or next_ref_id outside [-1, n_ref) cannot reach this call:
+ * hbam_decode_span ends the batch before such a record with HBAM_E_ARG under
+ * every stringency, HBAM_SILENT included (the kernels print "*" for one, and
+ * never index the name table with it).
+ * HBAM_E_STATE: no file ctx, a batch from several windows (format bounded
+ * batches), or a last batch from hbam_query_next or hbam_decode_writables.
+ * n >= 2^31 - 1 -> HBAM_E_ARG.  A failed device allocation -> HBAM_E_NOMEM. */
+int hbam_format_sam(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *offs, uint64_t *len);
 /* SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) for n serialized
  * values at once: value i = buf[offs[i], offs[i+1]) (the last ends at len), as
  * the shuffle frames them.  Decodes into out like hbam_decode_span (voff =
@@ -677,6 +735,12 @@ int hbam_gpu_fetch_encoded(hbam_gpu *g, uint64_t pos, uint64_t len, uint8_t *dst
  * the per-iteration HIP-event times of (sort words + radix sort, lengths +
  * scan, gather).  For measuring only. */
 int hbam_gpu_sort_writables(hbam_gpu *g, int32_t order, int32_t iters, float ms[3], uint64_t *bytes);
+/* hbam_format_sam of the records of the last run's last window into the same
+ * device buffer (hbam_gpu_fetch_encoded reads the text), iters timed times:
+ * ms = the per-iteration HIP-event times of (the measuring pass, the scan of
+ * the line lengths, the writing pass); *bytes = the text's size.  Errors as
+ * hbam_format_sam's.  For measuring only. */
+int hbam_gpu_format_sam(hbam_gpu *g, int32_t iters, float ms[3] /* measure, scan, write */, uint64_t *bytes);
 /* BGZF-compress the inflated stream of the last run (one window) on the GPU
  * with the loaded file's block boundaries (hbam_bgzf_compress semantics;
  * iters timed repetitions, HIP events); the result stays in HBM,
