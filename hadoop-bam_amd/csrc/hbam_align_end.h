@@ -6,28 +6,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hbam_dev_util.h"  // ldu32, wave_sum_u32, kWaveCigarOps
 #include "hbam_device.h"
 
 namespace hbam {
 
-// unaligned little-endian u32 from a 4-aligned base (reads 8 bytes: the
-// stream is padded), as hbam_kernels.hip
-__device__ __forceinline__ uint32_t ldu32(const uint8_t* base, uint64_t off) {
-  const uint32_t* p = reinterpret_cast<const uint32_t*>(base + (off & ~3ull));
-  uint32_t lo = p[0], hi = p[1];
-  return __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(off & 3));
-}
-
-constexpr uint32_t kWaveCigarOps = 32;  // longer cigars take a whole wave (record_invalid_wave's threshold)
-
 // M, D, N, =, X (op codes 0, 2, 3, 7, 8) consume the reference
 __device__ __forceinline__ bool consumes_ref(uint32_t op) { return (0x18du >> op) & 1u; }
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-  return v;
-}
 
 // Reference length of record i's cigar, wrapping like a Java int; 0 for a
 // lane with want == false.  One lane per record; a record whose cigar is

@@ -1,0 +1,1335 @@
+// hbam_chain.hip -- gfx950 kernels of the BAM record-boundary chain.
+//
+//   rec_cand / rec_walk / rec_search / rec_linkfix / rec_check   BAM
+//        record-boundary chain ([htsjdk] BAMRecordCodec.decode;
+//        SplittingBAMIndexer.java:340-368) with the STRICT isValid rules
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "hbam_dev_util.h"
+#include "hbam_device.h"
+#include "hbam_launch.h"
+#include "hbam_record_dev.h"
+
+namespace hbam {
+
+struct ChainEnv {  // (the device's part of ChainArgs: chain_env below)
+  const uint8_t* u;        // inflated stream
+  const BlockInfo* blocks;
+  uint64_t e_inf;          // end of inflated (available) data
+  uint64_t e_true;         // end of the logical stream (all blocks)
+  uint64_t p0;             // span start position (first record, read after seek)
+  uint64_t q_end;          // records with position >= q_end are outside the span
+  const uint64_t* dead;    // sorted dead positions (empty block after exhausted one)
+  uint32_t ndead;
+  int32_t n_ref;
+  uint32_t k0, k1;         // block range [k0, k1)
+  int validate;            // reader mode: 0 SILENT (none), 1 LENIENT (decode structure), 2 STRICT (SAMRecord.isValid)
+  const int32_t* ref_len;  // n_ref reference lengths, or nullptr
+};
+
+// ---------------------------------------------------------------------------
+// [htsjdk] SAMRecord.isValid under ValidationStringency.STRICT.  BAMFileReader's
+// iterator validates every record it returns unless the stringency is SILENT
+// (BAMRecordReader.java:142,192-194 pass hadoopbam.samheaderreader.
+// validation-stringency through; htsjdk's default is STRICT) and STRICT turns
+// the first error into a SAMFormatException.  Restated subset (DESIGN.md
+// §2.1; oracle/hbam_oracle.c orc_strict_invalid is the same rule list):
+//   structure  read name, cigar, seq, qual inside the record; cigar op <= 8
+//   unpaired   no proper-pair / mate-unmapped / mate-reverse / first / second
+//              flag, mate refID == -1
+//   paired     mate refID/pos consistent (isValidReferenceIndexAndPosition),
+//              mate refID set unless mate-unmapped, first or second flag
+//   unmapped   not secondary / supplementary, MAPQ 0, no cigar
+//   mapped     cigar present, non-empty sequence dictionary
+//   position   refID/pos consistent, pos+1 <= reference length
+//   cigar      Cigar.isValid (zero-length ops, H/S/P placement, I/D pairs,
+//              a real operator) and M/=/X blocks inside the reference
+//   bin        == reg2bin(alignmentStart-1, alignmentEnd)
+//   seq        cigar read length == l_seq when both are non-zero;
+//              l_seq == 0 needs FZ, or CQ + CS (unless secondary)
+// The reader's IllegalArgumentException (refID out of range) is checked
+// before this, as the record factory raises it first.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int reg2bin_dev(int beg, int end) {  // GenomicIndexUtil.regionToBin
+  --end;
+  if (beg >> 14 == end >> 14) return ((1 << 15) - 1) / 7 + (beg >> 14);
+  if (beg >> 17 == end >> 17) return ((1 << 12) - 1) / 7 + (beg >> 17);
+  if (beg >> 20 == end >> 20) return ((1 << 9) - 1) / 7 + (beg >> 20);
+  if (beg >> 23 == end >> 23) return ((1 << 6) - 1) / 7 + (beg >> 23);
+  if (beg >> 26 == end >> 26) return ((1 << 3) - 1) / 7 + (beg >> 26);
+  return 0;
+}
+
+// aux tag t present (an l_seq == 0 record's FZ / CQ / CS lookup); *zlen = Z
+// string length
+__device__ bool aux_find(const uint8_t* u, uint64_t a, uint64_t e, uint16_t tag, int64_t* zlen) {
+  while (a + 3 <= e) {
+    const uint16_t t = (uint16_t)(u[a] | (u[a + 1] << 8));
+    const uint8_t ty = u[a + 2];
+    a += 3;
+    int64_t sz;
+    switch (ty) {
+      case 'A': case 'c': case 'C': sz = 1; break;
+      case 's': case 'S': sz = 2; break;
+      case 'i': case 'I': case 'f': sz = 4; break;
+      case 'Z': case 'H': {
+        uint64_t j = a;
+        while (j < e && u[j]) ++j;
+        if (t == tag) *zlen = (int64_t)(j - a);
+        sz = (int64_t)(j - a) + 1;
+        break;
+      }
+      case 'B': {
+        if (a + 5 > e) return false;
+        const uint8_t sub = u[a];
+        const int32_t cnt = (int32_t)ldu32(u, a + 1);
+        const int es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+        if (cnt < 0) return false;
+        sz = 5 + (int64_t)cnt * es;
+        break;
+      }
+      default: return false;
+    }
+    if (t == tag) return true;
+    if ((uint64_t)sz > e - a) return false;  // a malformed aux block ends the lookup
+    a += (uint64_t)sz;
+  }
+  return false;
+}
+
+// true when the (fully inflated) record at q fails validation.  strict =
+// false keeps only the structural decode failures (LENIENT still decodes the
+// cigar for isValid and logs the rest).
+// *defer (when given): a cigar longer than kWaveCigarOps operators is not
+// checked here (false returned, *defer set) -- record_invalid_wave takes it.
+// (h: the record's head, load_head(E.u, q), already in registers)
+__device__ __forceinline__ bool record_invalid_h(const ChainEnv& E, uint64_t q, int32_t bs, bool strict, bool* defer,
+                                                 const RecHead& h) {
+  const uint8_t* u = E.u;
+  const int32_t ref = (int32_t)h.at(1), pos = (int32_t)h.at(2);
+  const uint32_t w12 = h.at(3), w16 = h.at(4);
+  const uint32_t lrn = w12 & 0xffu, mapq = (w12 >> 8) & 0xffu, bin = w12 >> 16;
+  const uint32_t ncig = w16 & 0xffffu, flag = w16 >> 16;
+  if (defer && ncig > kWaveCigarOps) {
+    *defer = true;
+    return false;
+  }
+  const int32_t lseq = (int32_t)h.at(5), nref = (int32_t)h.at(6), npos = (int32_t)h.at(7);
+  // structure: the lazy fields isValid decodes must lie inside the record
+  if (lrn < 1 || lseq < 0) return true;
+  const int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + ((int64_t)lseq + 1) / 2 + (int64_t)lseq;
+  if (need > (int64_t)bs) return true;
+  const uint64_t c0 = q + 36 + lrn;
+  uint32_t qlen = 0, rlen = 0;
+  for (uint32_t k = 0; k < ncig; ++k) {
+    const uint32_t op = ldu32(u, c0 + 4ull * k) & 0xfu;
+    if (op > 8) return true;
+  }
+  if (!strict) return false;
+  const bool paired = flag & 0x1, unmapped = flag & 0x4;
+  if (!paired) {
+    if (flag & (0x2 | 0x8 | 0x20 | 0x40 | 0x80)) return true;
+    if (nref != -1) return true;
+  } else {
+    if (nref == -1) {
+      if (npos != -1) return true;
+      if (!(flag & 0x8)) return true;  // "Mapped mate should have mate reference name"
+    } else {
+      if (npos == -1) return true;
+      if (E.ref_len && (int64_t)npos + 1 > (int64_t)E.ref_len[nref]) return true;
+    }
+    if (!(flag & 0xC0)) return true;  // neither first nor second of pair
+  }
+  if (unmapped) {
+    if (flag & (0x100 | 0x800)) return true;
+    if (mapq != 0) return true;  // (a cigar on an unmapped read is allowed: test.bam has them)
+  } else {
+    if (ncig == 0) return true;
+    if (E.n_ref == 0) return true;  // MISSING_SEQUENCE_DICTIONARY
+  }
+  if (ref == -1) {
+    if (pos != -1) return true;
+  } else {
+    if (pos == -1) return true;
+    if (E.ref_len && (int64_t)pos + 1 > (int64_t)E.ref_len[ref]) return true;
+  }
+  // cigar: Cigar.isValid + alignment blocks (mapped reads only)
+  bool real = false;
+  int64_t rpos = (int64_t)pos + 1, maxend = 0;
+  uint32_t prev_op = 99, first_op = 99, last_op = 99;
+  if (ncig) {
+    first_op = ldu32(u, c0) & 0xfu;
+    last_op = ldu32(u, c0 + 4ull * (ncig - 1)) & 0xfu;
+  }
+  // Cigar.isValid: between two separators (M/=/X/N or P) an I or a D may
+  // appear only once ("No M or N operator between pair of I/D operators")
+  bool seen_i = false, seen_d = false;
+  for (uint32_t k = 0; k < ncig; ++k) {
+    const uint32_t c = ldu32(u, c0 + 4ull * k), op = c & 0xfu, len = c >> 4;
+    const bool consumes_read = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;
+    const bool consumes_ref = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
+    if (consumes_read) qlen += len;
+    if (consumes_ref) rlen += len;
+    if (!unmapped) {
+      if (len == 0) return true;
+      if (op == 5) {
+        if (k != 0 && k != ncig - 1) return true;
+      } else if (op == 4) {
+        if (k == 0 || k == ncig - 1) {
+        } else if (k == 1) {
+          if (!(ncig == 3 && last_op == 5) && first_op != 5) return true;
+        } else if (k == ncig - 2) {
+          if (last_op != 5) return true;
+        } else {
+          return true;
+        }
+      } else if (op == 6) {
+        if (k != 0) {
+          if (k == ncig - 1) return true;
+          const uint32_t nx = ldu32(u, c0 + 4ull * (k + 1)) & 0xfu;
+          const bool pr = prev_op <= 3 || prev_op == 7 || prev_op == 8, nr = nx <= 3 || nx == 7 || nx == 8;
+          if (!pr || !nr) return true;
+        }
+        seen_i = seen_d = false;
+      } else {  // real operator
+        real = true;
+        if (op == 1) {
+          if (seen_i) return true;
+          seen_i = true;
+        } else if (op == 2) {
+          if (seen_d) return true;
+          seen_d = true;
+        } else {
+          seen_i = seen_d = false;
+        }
+        if (op == 0 || op == 7 || op == 8) maxend = max(maxend, rpos + (int64_t)len - 1);
+      }
+    }
+    if (consumes_ref) rpos += len;
+    prev_op = op;
+  }
+  if (!unmapped) {
+    if (!real) return true;
+    if (ref >= 0 && E.ref_len && maxend > (int64_t)E.ref_len[ref]) return true;  // CIGAR_MAPS_OFF_REFERENCE
+  }
+  // bin: computeIndexingBin()
+  {
+    const int start0 = pos;  // getAlignmentStart() - 1
+    int end = unmapped ? 0 : (int)((int64_t)pos + 1 + (int64_t)rlen - 1);
+    if (end <= 0) end = start0 + 1;
+    if ((uint32_t)reg2bin_dev(start0, end) != bin) return true;
+  }
+  if (lseq != 0 && ncig != 0 && (int64_t)qlen != (int64_t)lseq) return true;  // MISMATCH_CIGAR_SEQ_LENGTH
+  if (lseq == 0 && !(flag & 0x100)) {  // EMPTY_READ unless FZ, or CQ and CS
+    const uint64_t a0 = c0 + 4ull * ncig, ae = q + 4 + (uint64_t)bs;
+    int64_t zl = -1;
+    if (!aux_find(u, a0, ae, (uint16_t)('F' | ('Z' << 8)), &zl)) {
+      int64_t cq = -1, cs = -1;
+      const bool hq = aux_find(u, a0, ae, (uint16_t)('C' | ('Q' << 8)), &cq);
+      const bool hs = aux_find(u, a0, ae, (uint16_t)('C' | ('S' << 8)), &cs);
+      if (!hq || !hs || cq <= 0 || cs <= 0) return true;
+    }
+  }
+  return false;
+}
+
+__device__ bool record_invalid(const ChainEnv& E, uint64_t q, int32_t bs, bool strict, bool* defer = nullptr) {
+  return record_invalid_h(E, q, bs, strict, defer, load_head(E.u, q));
+}
+
+// record_invalid by a whole wave, for records with long cigars (ONT-like
+// reads carry thousands of operators; one lane walking them serially set the
+// pace of the record check: 2.0 ms per C4 pass).  Same rules, same result: the
+// per-operator rules become a lane-per-operator pass over chunks of 64, the
+// running state becomes scans --
+//   qlen / rlen            wrapping u32 sums (as the serial u32 accumulators)
+//   alignment block ends   exclusive 64-bit sum of reference lengths before k
+//   Cigar.isValid I/D pairs   an I (D) is invalid when the previous I (D)
+//                          comes after the last separator (M N = X P) before it:
+//                          two running max-scans of 1-based indices.
+// Wave-uniform arguments; returns the same value on every lane.
+__device__ bool record_invalid_wave(const ChainEnv& E, uint64_t q, int32_t bs, bool strict) {
+  const uint8_t* u = E.u;
+  const uint32_t lane = lane_id();
+  const int32_t ref = (int32_t)ldu32(u, q + 4), pos = (int32_t)ldu32(u, q + 8);
+  const uint32_t w12 = ldu32(u, q + 12), w16 = ldu32(u, q + 16);
+  const uint32_t lrn = w12 & 0xffu, mapq = (w12 >> 8) & 0xffu, bin = w12 >> 16;
+  const uint32_t ncig = w16 & 0xffffu, flag = w16 >> 16;
+  const int32_t lseq = (int32_t)ldu32(u, q + 20), nref = (int32_t)ldu32(u, q + 24), npos = (int32_t)ldu32(u, q + 28);
+  if (lrn < 1 || lseq < 0) return true;
+  const int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + ((int64_t)lseq + 1) / 2 + (int64_t)lseq;
+  if (need > (int64_t)bs) return true;
+  const uint64_t c0 = q + 36 + lrn;
+  bool bad = false;
+  for (uint32_t k = lane; k < ncig; k += 64) bad |= (ldu32(u, c0 + 4ull * k) & 0xfu) > 8;
+  if (__ballot(bad)) return true;
+  if (!strict) return false;
+  const bool paired = flag & 0x1, unmapped = flag & 0x4;
+  if (!paired) {
+    if (flag & (0x2 | 0x8 | 0x20 | 0x40 | 0x80)) return true;
+    if (nref != -1) return true;
+  } else {
+    if (nref == -1) {
+      if (npos != -1) return true;
+      if (!(flag & 0x8)) return true;
+    } else {
+      if (npos == -1) return true;
+      if (E.ref_len && (int64_t)npos + 1 > (int64_t)E.ref_len[nref]) return true;
+    }
+    if (!(flag & 0xC0)) return true;
+  }
+  if (unmapped) {
+    if (flag & (0x100 | 0x800)) return true;
+    if (mapq != 0) return true;
+  } else {
+    if (ncig == 0) return true;
+    if (E.n_ref == 0) return true;
+  }
+  if (ref == -1) {
+    if (pos != -1) return true;
+  } else {
+    if (pos == -1) return true;
+    if (E.ref_len && (int64_t)pos + 1 > (int64_t)E.ref_len[ref]) return true;
+  }
+  const uint32_t first_op = ncig ? ldu32(u, c0) & 0xfu : 99u;
+  const uint32_t last_op = ncig ? ldu32(u, c0 + 4ull * (ncig - 1)) & 0xfu : 99u;
+  uint32_t qlen = 0, rlen = 0;          // lane partial sums (wrapping, as the serial code)
+  uint64_t rcarry = 0;                  // reference bases of the chunks before
+  uint32_t sep_carry = 0, i_carry = 0, d_carry = 0;  // 1-based indices of the last separator / I / D
+  bool real = false;
+  int64_t maxend = 0;
+  for (uint32_t k0 = 0; k0 < ncig; k0 += 64) {
+    const uint32_t k = k0 + lane;
+    const bool in = k < ncig;
+    const uint32_t c = in ? ldu32(u, c0 + 4ull * k) : 0u, op = in ? c & 0xfu : 15u, len = c >> 4;
+    const bool consumes_read = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;
+    const bool consumes_ref = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
+    if (consumes_read) qlen += len;
+    if (consumes_ref) rlen += len;
+    const uint64_t rl = consumes_ref ? (uint64_t)len : 0ull;
+    const uint64_t rincl = wave_incl_sum64(rl);
+    const int64_t rpos = (int64_t)pos + 1 + (int64_t)(rcarry + rincl - rl);  // before op k
+    rcarry += (uint64_t)__builtin_amdgcn_readlane((int)(uint32_t)rincl, 63) |
+              ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rincl >> 32), 63) << 32);
+    // running 1-based indices (0 = none) up to and including op k
+    const bool sep = op == 0 || op == 3 || op == 6 || op == 7 || op == 8;
+    const uint32_t sep_i = max(sep_carry, wave_incl_max_dpp(sep ? k + 1 : 0u));
+    const uint32_t i_i = max(i_carry, wave_incl_max_dpp(op == 1 ? k + 1 : 0u));
+    const uint32_t d_i = max(d_carry, wave_incl_max_dpp(op == 2 ? k + 1 : 0u));
+    // the same before op k (exclusive): one lane up, the carry on lane 0
+    uint32_t sep_x = (uint32_t)__shfl_up((int)sep_i, 1, 64), i_x = (uint32_t)__shfl_up((int)i_i, 1, 64),
+             d_x = (uint32_t)__shfl_up((int)d_i, 1, 64);
+    if (lane == 0) {
+      sep_x = sep_carry;
+      i_x = i_carry;
+      d_x = d_carry;
+    }
+    sep_carry = (uint32_t)__builtin_amdgcn_readlane((int)sep_i, 63);
+    i_carry = (uint32_t)__builtin_amdgcn_readlane((int)i_i, 63);
+    d_carry = (uint32_t)__builtin_amdgcn_readlane((int)d_i, 63);
+    if (in && !unmapped) {
+      if (len == 0) bad = true;
+      if (op == 5) {
+        if (k != 0 && k != ncig - 1) bad = true;
+      } else if (op == 4) {
+        if (k == 0 || k == ncig - 1) {
+        } else if (k == 1) {
+          if (!(ncig == 3 && last_op == 5) && first_op != 5) bad = true;
+        } else if (k == ncig - 2) {
+          if (last_op != 5) bad = true;
+        } else {
+          bad = true;
+        }
+      } else if (op == 6) {
+        if (k != 0) {
+          if (k == ncig - 1) {
+            bad = true;
+          } else {
+            const uint32_t pv = ldu32(u, c0 + 4ull * (k - 1)) & 0xfu, nx = ldu32(u, c0 + 4ull * (k + 1)) & 0xfu;
+            const bool pr = pv <= 3 || pv == 7 || pv == 8, nr = nx <= 3 || nx == 7 || nx == 8;
+            if (!pr || !nr) bad = true;
+          }
+        }
+      } else {  // real operator
+        real = true;
+        if (op == 1 && i_x > sep_x) bad = true;  // a second I since the last separator
+        if (op == 2 && d_x > sep_x) bad = true;
+        if (op == 0 || op == 7 || op == 8) maxend = max(maxend, rpos + (int64_t)len - 1);
+      }
+    }
+  }
+  if (__ballot(bad)) return true;
+  qlen = wave_sum_u32(qlen);
+  rlen = wave_sum_u32(rlen);
+  if (!unmapped) {
+    if (__ballot(real) == 0) return true;
+    maxend = wave_max_i64(maxend);
+    if (ref >= 0 && E.ref_len && maxend > (int64_t)E.ref_len[ref]) return true;
+  }
+  {
+    const int start0 = pos;
+    int end = unmapped ? 0 : (int)((int64_t)pos + 1 + (int64_t)rlen - 1);
+    if (end <= 0) end = start0 + 1;
+    if ((uint32_t)reg2bin_dev(start0, end) != bin) return true;
+  }
+  if (lseq != 0 && ncig != 0 && (int64_t)qlen != (int64_t)lseq) return true;
+  if (lseq == 0 && !(flag & 0x100)) {
+    const uint64_t a0 = c0 + 4ull * ncig, ae = q + 4 + (uint64_t)bs;
+    int64_t zl = -1;
+    if (!aux_find(u, a0, ae, (uint16_t)('F' | ('Z' << 8)), &zl)) {
+      int64_t cq = -1, cs = -1;
+      const bool hq = aux_find(u, a0, ae, (uint16_t)('C' | ('Q' << 8)), &cq);
+      const bool hs = aux_find(u, a0, ae, (uint16_t)('C' | ('S' << 8)), &cs);
+      if (!hq || !hs || cq <= 0 || cs <= 0) return true;
+    }
+  }
+  return false;
+}
+
+__device__ __forceinline__ bool is_dead(const ChainEnv& E, uint64_t q) {
+  uint32_t lo = 0, hi = E.ndead;  // sorted; usually 0 or 1 entries (the EOF marker)
+  while (lo < hi) {
+    uint32_t mid = (lo + hi) >> 1;
+    if (E.dead[mid] < q) lo = mid + 1; else hi = mid;
+  }
+  return lo < E.ndead && E.dead[lo] == q;
+}
+__device__ __forceinline__ bool dead_in_record(const ChainEnv& E, uint64_t q, int32_t bs) {
+  if (E.ndead == 0) return false;
+  const uint8_t offs[11] = {4, 8, 12, 13, 14, 16, 18, 20, 24, 28, 32};
+  for (int i = 0; i < 11; ++i)
+    if (is_dead(E, q + offs[i])) return true;
+  return bs > 32 && is_dead(E, q + 36);
+}
+
+// Is any dead position within [q, q + 40] (header fields + first rest byte)?
+__device__ __forceinline__ bool dead_near(const ChainEnv& E, uint64_t q) {
+  uint32_t lo = 0, hi = E.ndead;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (E.dead[mid] < q) lo = mid + 1; else hi = mid;
+  }
+  return lo < E.ndead && E.dead[lo] <= q + 40;
+}
+
+// Necessary conditions for a record of a well-formed BAM (guess only; the
+// true chain is fixed by the link step, never by this test).  Bytes past the
+// inflated range of a stream that goes on (an open window, or blocks not yet
+// inflated) cannot refute a record: it stays plausible when its block_size
+// can be read and is >= 32 (so a walk through it still moves forward).
+// (Taken as implausible, the record straddling a window's end within its
+// first 36 + l_read_name bytes failed every candidate walk of its block, and
+// the block's search walked from every later candidate: ~7 ms on one 256 MiB
+// drop-in window.)
+__device__ __forceinline__ bool plausible(const ChainEnv& E, uint64_t q) {
+  if (q + 36 > E.e_inf) return E.e_inf < E.e_true && q + 4 <= E.e_inf && (int32_t)ldu32(E.u, q) >= 32;
+  const RecHead h = load_head(E.u, q);
+  int32_t bs = (int32_t)h.at(0);
+  int32_t ref = (int32_t)h.at(1);
+  int32_t pos = (int32_t)h.at(2);
+  uint32_t lrn = h.at(3) & 0xffu;
+  uint32_t ncig = h.at(4) & 0xffffu;
+  int32_t lseq = (int32_t)h.at(5);
+  int32_t nref = (int32_t)h.at(6);
+  int32_t npos = (int32_t)h.at(7);
+  if (ref < -1 || ref >= E.n_ref || nref < -1 || nref >= E.n_ref) return false;
+  if (pos < -1 || npos < -1 || lrn < 1 || lseq < 0) return false;
+  int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + (int64_t)lseq + ((int64_t)lseq + 1) / 2;
+  if ((int64_t)bs < need) return false;
+  if (q + 4 + (uint64_t)bs > E.e_true) return false;
+  if (q + 36 + lrn > E.e_inf) return E.e_inf < E.e_true;
+  return E.u[q + 36 + lrn - 1] == 0;
+}
+
+// plausible() split for a software-pipelined walk: plausible_head decides
+// from q's head h alone (1: plausible, 0: not, 2: the read-name end byte at
+// q + 36 + lrn - 1 decides: *name_at = its position), so that a walk can
+// load that byte together with the next record's head (q + 4 + block_size):
+// one dependent memory round trip per record instead of two.  Same result
+// as plausible(E, q) when h = load_head(E.u, q).
+__device__ __forceinline__ int plausible_head(const ChainEnv& E, uint64_t q, const RecHead& h, uint64_t* name_at) {
+  if (q + 36 > E.e_inf) return E.e_inf < E.e_true && q + 4 <= E.e_inf && (int32_t)h.at(0) >= 32;
+  int32_t bs = (int32_t)h.at(0);
+  int32_t ref = (int32_t)h.at(1);
+  int32_t pos = (int32_t)h.at(2);
+  uint32_t lrn = h.at(3) & 0xffu;
+  uint32_t ncig = h.at(4) & 0xffffu;
+  int32_t lseq = (int32_t)h.at(5);
+  int32_t nref = (int32_t)h.at(6);
+  int32_t npos = (int32_t)h.at(7);
+  if (ref < -1 || ref >= E.n_ref || nref < -1 || nref >= E.n_ref) return 0;
+  if (pos < -1 || npos < -1 || lrn < 1 || lseq < 0) return 0;
+  int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + (int64_t)lseq + ((int64_t)lseq + 1) / 2;
+  if ((int64_t)bs < need) return 0;
+  if (q + 4 + (uint64_t)bs > E.e_true) return 0;
+  if (q + 36 + lrn > E.e_inf) return E.e_inf < E.e_true;
+  *name_at = q + 36 + lrn - 1;
+  return 2;
+}
+
+// plausible() at q and at the record after it (or the end / unreadable data):
+// a cheap second check that removes most false candidates inside long records.
+__device__ __forceinline__ bool plausible2(const ChainEnv& E, uint64_t q) {
+  if (!plausible(E, q)) return false;
+  const uint64_t q2 = q + 4 + (uint64_t)(int32_t)ldu32(E.u, q);
+  return q2 == E.e_true || q2 + 36 > E.e_inf || plausible(E, q2);
+}
+
+// A necessary condition of plausible() that reads 8 bytes: refID and mate
+// refID in range (random bytes pass with probability ~(n_ref / 2^32)^2), or
+// data past the inflated range, which plausible() judges itself.  Candidate
+// scans test it first and run plausible2 only when a lane of the wave passes.
+__device__ __forceinline__ bool cand_prefilter(const ChainEnv& E, uint64_t q) {
+  if (q + 36 > E.e_inf) return true;
+  const int32_t ref = (int32_t)ldu32(E.u, q + 4), nref = (int32_t)ldu32(E.u, q + 24);
+  return ref >= -1 && ref < E.n_ref && nref >= -1 && nref < E.n_ref;
+}
+
+// One chain step from q under the given rules.  Returns false if the walk
+// cannot continue (data unavailable or malformed record); *nq = next position.
+template <int MODE>
+__device__ __forceinline__ bool chain_step(const ChainEnv& E, uint64_t q, uint64_t* nq) {
+  if (q + 4 > E.e_inf) return false;
+  int32_t bs = (int32_t)ldu32(E.u, q);
+  if (MODE == kReader) {
+    if (bs < 32) return false;
+    *nq = q + 4 + (uint64_t)bs;
+  } else {
+    *nq = q + 4 + (bs > 0 ? (uint64_t)bs : 0);
+  }
+  return true;
+}
+
+// Link the per-block guesses into the true chain (serial in block order, with
+// a 256-block tile fast path when every block of the tile links to the next).
+// entry[i] = true first record position of block k0+i, or kNone.
+// summary[0] = final chain position, summary[1] = 1 if the chain stopped
+// inside a block (malformed record / data unavailable).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_rec_link(ChainEnv E, const uint64_t* __restrict__ g,
+                                                  const uint64_t* __restrict__ x, uint64_t* __restrict__ entry,
+                                                  uint64_t* __restrict__ summary) {
+  __shared__ uint64_t s_cur;
+  __shared__ int s_stop;
+  const uint32_t nb = E.k1 - E.k0;
+  if (threadIdx.x == 0) { s_cur = E.p0; s_stop = 0; }
+  __syncthreads();
+  for (uint32_t t0 = 0; t0 < nb; t0 += 256) {
+    const uint32_t i = t0 + threadIdx.x;
+    const uint64_t cur = s_cur;
+    const int stop = s_stop;
+    bool fast = true;
+    if (i < nb) {
+      const BlockInfo b = E.blocks[E.k0 + i];
+      const uint64_t bend = b.ustart + b.isize;
+      const uint64_t gi = g[i], xi = x[i];
+      const uint64_t expect = (threadIdx.x == 0) ? cur : x[i - 1];
+      fast = !stop && gi != kNone && gi == expect && gi < E.q_end && xi != kNone && xi >= bend;
+    }
+    const int all_fast = __syncthreads_and(fast);
+    if (all_fast) {
+      if (i < nb) entry[i] = g[i];
+      __syncthreads();
+      if (threadIdx.x == 0) s_cur = x[min(t0 + 255, nb - 1)];
+      __syncthreads();
+      continue;
+    }
+    if (threadIdx.x == 0) {
+      uint64_t c = cur;
+      int st = stop;
+      for (uint32_t j = t0; j < min(t0 + 256, nb); ++j) {
+        const BlockInfo b = E.blocks[E.k0 + j];
+        const uint64_t bend = b.ustart + b.isize;
+        if (st || c >= E.q_end || c >= bend || b.isize == 0) {
+          entry[j] = kNone;
+          continue;
+        }
+        entry[j] = c;
+        if (g[j] == c) {
+          c = x[j];
+        } else {
+          uint64_t q = c, nq;
+          while (q < bend && chain_step<MODE>(E, q, &nq)) q = nq;
+          c = q;
+        }
+        if (c < bend) st = 1;
+      }
+      s_cur = c;
+      s_stop = st;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    summary[0] = s_cur;
+    summary[1] = (uint64_t)s_stop;
+  }
+}
+
+// Parallel link.  y[i] = guess exit of block i (0 when the block has no
+// guess); in[i] = max(y[0..i-1]) is the position the chain enters block i
+// with, IF every guess is on the true chain.  k_rec_link_check verifies that
+// claim block by block (entry = guess where the chain enters the block,
+// pass-through elsewhere) and counts violations; any violation sends the span
+// to the exact serial link (k_rec_link).
+__global__ void k_rec_link_y(const uint64_t* __restrict__ g, const uint64_t* __restrict__ x, uint32_t nb,
+                             uint64_t* __restrict__ y) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb) y[i] = (g[i] != kNone && x[i] != kNone) ? x[i] : 0;
+}
+
+// Count (and validate) the records of each block of the span under the
+// reader / indexer rules.  One thread per block.
+//   cnt[i], err[i] = status code, errpos[i] = position of the failing record,
+//   *need = furthest byte the span needs inflated (atomicMax).
+template <int MODE>
+__global__ void k_rec_count(ChainEnv E, const uint64_t* __restrict__ entry, uint32_t* __restrict__ cnt,
+                            int32_t* __restrict__ err, unsigned long long* __restrict__ need) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t nb = E.k1 - E.k0;
+  if (i >= nb) return;
+  uint32_t n = 0;
+  int st = kOk;
+  const uint64_t e = entry[i];
+  if (e != kNone) {
+    const BlockInfo b = E.blocks[E.k0 + i];
+    const uint64_t lim = min(b.ustart + b.isize, E.q_end);
+    uint64_t q = e;
+    bool first = (MODE == kReader) && (e == E.p0);  // reader: first record follows a seek
+    while (q < lim) {
+      if (!first && is_dead(E, q)) {  // readInt at an exhausted block + empty block: EOF
+        st = kStopClean;
+        break;
+      }
+      first = false;
+      const uint64_t avail = E.e_true - q;
+      if (avail < 4) {
+        st = MODE == kIndexer && avail > 0 ? kErrIO : kStopClean;  // "less than 4 bytes long" / EOF
+        break;
+      }
+      if (q + 4 > E.e_inf) { atomicMax(need, (unsigned long long)(q + 4)); break; }
+      const int32_t bs = (int32_t)ldu32(E.u, q);
+      if (MODE == kReader) {
+        if (bs < 32) { st = kErrFormat; break; }
+        if (dead_in_record(E, q, bs) || avail - 4 < (uint64_t)bs) { st = kErrTrunc; break; }
+        if (q + 4 + (uint64_t)bs > E.e_inf) { atomicMax(need, (unsigned long long)(q + 4 + (uint64_t)bs)); break; }
+        const int32_t ref = (int32_t)ldu32(E.u, q + 4), nref = (int32_t)ldu32(E.u, q + 24);
+        if (ref < -1 || ref >= E.n_ref || nref < -1 || nref >= E.n_ref) { st = kErrArg; break; }
+        if (E.validate && record_invalid(E, q, bs, E.validate == 2)) { st = kErrFormat; break; }
+        ++n;
+        q += 4 + (uint64_t)bs;
+      } else {
+        ++n;
+        if (bs > 0) {
+          if ((uint64_t)bs > avail - 4 || is_dead(E, q + 4)) { st = kErrIO; break; }  // "Skip failed"
+          q += 4 + (uint64_t)bs;
+        } else {
+          q += 4;
+        }
+      }
+    }
+  }
+  cnt[i] = n;
+  err[i] = st;
+}
+
+// Second walk: write record positions and normalized voffs at base[i].
+template <int MODE>
+__global__ void k_rec_emit(ChainEnv E, const uint64_t* __restrict__ entry, const uint32_t* __restrict__ cnt,
+                           const uint64_t* __restrict__ base, uint64_t* __restrict__ rec_pos,
+                           uint64_t* __restrict__ rec_voff) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t nb = E.k1 - E.k0;
+  if (i >= nb) return;
+  const uint32_t n = cnt[i];
+  if (n == 0) return;
+  const BlockInfo b = E.blocks[E.k0 + i];
+  uint64_t q = entry[i];
+  uint64_t o = base[i];
+  for (uint32_t r = 0; r < n; ++r) {
+    rec_pos[o + r] = q;
+    rec_voff[o + r] = (b.coff << 16) | (q - b.ustart);
+    const int32_t bs = (int32_t)ldu32(E.u, q);
+    q += 4 + (uint64_t)(MODE == kReader ? bs : (bs > 0 ? bs : 0));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Record chain v2: lane-per-block walks with per-block record lists
+// ---------------------------------------------------------------------------
+//   k_rec_cand     one wave per block: first plausible record start (512
+//                  positions per step) -- where the block's guess walk begins.
+//   k_rec_walk     one lane per block: the chain from that candidate (next
+//                  candidates on failure), from the span start, or from a
+//                  forced (true) entry; every record start of the block is
+//                  listed as a u16 offset.  All walks of a span are in flight
+//                  at once, so the span costs one dependent-load chain of
+//                  ~records-per-block steps instead of a wave per block.
+//   k_rec_linkfix  max-scan link check; blocks whose list is off the chain are
+//                  re-walked from their true entry (usually zero or a few).
+//   k_rec_check_out  one wave per block: the reader / indexer rules of
+//                  k_rec_count for every listed record at once (the first stop
+//                  gives count, status and the bytes still to inflate), then
+//                  positions, voffs and (reader) the fused decode + key at the
+//                  block's scanned base.
+// k_rec_cand: one wave per block, each lane testing kCandPos consecutive
+// positions per step (512 per step): refID and mate refID of its 8 positions
+// come from 5 aligned 8 B loads, and only the rare position that passes that
+// test runs plausible2; the first hit wins (ballot).  A short-read block
+// finishes in its first step, at the cost of the old 64-positions step; a
+// long-read block (C4: the first record start lies ~32 KB in on average)
+// takes 8x fewer dependent steps (0.74 ms per C4 pass before).
+constexpr int kCandPos = 8;
+template <int MODE>
+__global__ __launch_bounds__(64) void k_rec_cand(ChainEnv E, uint64_t* __restrict__ cand) {
+  const uint32_t k = E.k0 + blockIdx.x;
+  const BlockInfo b = E.blocks[k];
+  const uint64_t bend = b.ustart + b.isize;
+  const uint32_t lane = lane_id();
+  uint64_t c = kNone;
+  if (bend > E.p0 && b.ustart > E.p0 && b.ustart < E.q_end && b.isize > 0) {
+    const uint64_t s0 = b.ustart & ~7ull;  // 8-aligned scan origin (positions < ustart are masked)
+    for (uint64_t c0 = s0; c0 < bend; c0 += 64 * kCandPos) {
+      const uint64_t p0 = c0 + (uint64_t)lane * kCandPos;
+      uint32_t pass = 0;  // bit j: position p0 + j passes the prefilter
+      if (p0 < bend) {
+        uint32_t w[10];
+        const uint2* src = reinterpret_cast<const uint2*>(E.u + p0);  // du_ is padded past the stream
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+          const uint2 v = src[i];
+          w[2 * i] = v.x;
+          w[2 * i + 1] = v.y;
+        }
+#pragma unroll
+        for (int j = 0; j < kCandPos; ++j) {
+          const uint64_t q = p0 + j;
+          const int32_t ref = (int32_t)__builtin_amdgcn_alignbyte(w[2 + (j >> 2)], w[1 + (j >> 2)], j & 3);
+          const int32_t nref = (int32_t)__builtin_amdgcn_alignbyte(w[7 + (j >> 2)], w[6 + (j >> 2)], j & 3);
+          const bool ok = q >= b.ustart && q < bend &&
+                          (q + 36 > E.e_inf || (ref >= -1 && ref < E.n_ref && nref >= -1 && nref < E.n_ref));
+          pass |= ok ? 1u << j : 0u;
+        }
+      }
+      uint32_t hit = kCandPos;  // the first position of this lane that is plausible2
+      if (__ballot(pass != 0)) {
+        for (uint32_t m = pass; m; m &= m - 1) {
+          const uint32_t j = (uint32_t)__ffs((int)m) - 1;
+          if (plausible2(E, p0 + j)) {
+            hit = j;
+            break;
+          }
+        }
+      }
+      const uint64_t hm = __ballot(hit < kCandPos);
+      if (hm) {
+        const uint32_t f = (uint32_t)__ffsll((long long)hm) - 1;
+        c = c0 + (uint64_t)f * kCandPos + (uint32_t)__shfl((int)hit, (int)f, 64);
+        break;
+      }
+    }
+    // A start 1-3 bytes before a true record reads that record's block_size
+    // shifted up by whole bytes (~2^8-2^24 times it) and, with refID 0, its
+    // fields stay in range: plausible2 passes and the walk leaves the block
+    // at once -- past the inflated end of a window it cannot be checked, and
+    // the link check then re-walks the block and the ones its far exit hid
+    // (one round each; C2 passes took two, drop-in windows fell back to the
+    // serial link).  When c's record leaves the block, a plausible2 start
+    // 1-3 bytes later whose record ends inside the block is taken instead.
+    if (c != kNone && lane == 0 && c + 4 + (uint64_t)(int32_t)ldu32(E.u, c) >= bend) {
+      for (uint32_t d = 1; d <= 3; ++d) {
+        const uint64_t q = c + d;
+        if (q + 36 <= E.e_inf && q + 4 + (uint64_t)(int32_t)ldu32(E.u, q) < bend && plausible2(E, q)) {
+          c = q;
+          break;
+        }
+      }
+    }
+  }
+  if (lane == 0) cand[blockIdx.x] = c;
+}
+
+constexpr int kGuessLookahead = 4;  // plausible records required past a guess walk's exit
+constexpr uint64_t kRetry = ~0ull - 2;  // g[]: the candidate's walk failed, search on
+constexpr uint32_t kListPlausible = 0x80000000u;  // wcnt flag: the list came from a plausible() walk
+constexpr uint32_t kListCountMask = 0x7fffffffu;
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __restrict__ cand,
+                                                  const uint64_t* __restrict__ force, uint64_t* __restrict__ g_out,
+                                                  uint64_t* __restrict__ x_out, uint32_t* __restrict__ wcnt,
+                                                  uint16_t* __restrict__ list, uint32_t* __restrict__ overflow,
+                                                  bool validate) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t nb = E.k1 - E.k0;
+  if (force) {
+    // A re-walk round forces a few blocks; each is one lane's chain of ~190
+    // dependent loads from HBM.  The whole wave first pulls every forced
+    // block of the wave (+ the lookahead past its end) into L2 with
+    // independent loads, so the chain then runs at L2 latency.
+    const uint64_t fi = i < nb ? force[i] : kNone;
+    uint64_t todo = __ballot(fi != kNone && fi != kForceEmpty);
+    uint32_t acc = 0;
+    const uint32_t lane = lane_id();
+    while (todo) {
+      const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const BlockInfo wb = E.blocks[E.k0 + blockIdx.x * blockDim.x + (threadIdx.x & ~63u) + src];
+      const uint64_t lo = wb.ustart & ~127ull;
+      const uint64_t hi = min(wb.ustart + wb.isize + 4096, E.e_inf);
+      for (uint64_t a = lo + 128ull * lane; a < hi; a += 128ull * 64) acc += ldu32(E.u, a);
+    }
+    if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
+  }
+  if (i >= nb) return;
+  uint64_t f = kNone;  // guess
+  if (force) {
+    f = force[i];
+    if (f == kNone) return;  // keep this block's walk
+  }
+  const BlockInfo b = E.blocks[E.k0 + i];
+  const uint64_t bend = b.ustart + b.isize;
+  if (validate && f != kForceEmpty && f != kNone) {
+    // a link-round entry may itself come from a wrong walk upstream (fixed in
+    // the same round): re-walk only if the chain from it is plausible to the
+    // block end and beyond; otherwise keep the old walk for the next round
+    uint64_t q = f;
+    bool ok = true;
+    int extra = 0;
+    while (ok) {
+      if (q >= bend && (extra++ >= kGuessLookahead || q == E.e_true || q + 36 > E.e_inf)) break;
+      if (!plausible(E, q)) ok = false;
+      else q += 4 + (uint64_t)(int32_t)ldu32(E.u, q);
+    }
+    if (!ok) return;
+  }
+  uint16_t* __restrict__ L = list + (uint64_t)i * kListCap;
+  uint64_t g = kNone, x = kNone;
+  uint32_t n = 0;
+  bool plaus_list = false;  // every listed record passed plausible()
+  const bool live = bend > E.p0 && b.ustart < E.q_end && b.isize > 0;
+  if (live && f != kForceEmpty) {
+    uint64_t entry = f;
+    if (f == kNone && b.ustart <= E.p0) entry = E.p0;  // the block of the span start: entry known
+    if (entry != kNone) {
+      g = entry;
+      uint64_t q = entry, nq;
+      while (q < bend) {
+        if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
+        ++n;
+        if (!chain_step<MODE>(E, q, &nq)) break;
+        q = nq;
+      }
+      x = q;
+    } else {
+      const uint64_t c = cand[i];
+      if (c < bend) {  // c == kNone (no candidate): nothing to walk
+        // software-pipelined: record q's read-name end byte and the next
+        // record's head are loaded together (plausible_head), one dependent
+        // round trip per record.  Loads past the inflated range read the
+        // stream's padding and are not used (plausible_head's rules).
+        uint64_t q = c, exitq = c;
+        uint32_t m = 0;
+        bool valid = true;
+        RecHead h = load_head(E.u, q);
+        int left = kGuessLookahead;  // plausible records required past the block end
+        for (;;) {
+          const bool inside = q < bend;
+          if (!inside && (left-- <= 0 || q == E.e_true || q + 36 > E.e_inf)) break;
+          uint64_t na = q;
+          const int ph = plausible_head(E, q, h, &na);
+          const uint64_t q2 = q + 4 + (uint64_t)(int32_t)h.at(0);
+          const uint8_t nb = E.u[na];
+          // (q2 may lie anywhere: its head is loaded when its block_size is
+          // inflated; reads reach 40 bytes past it, inside the stream's pad)
+          h = load_head(E.u, q2 + 4 <= E.e_inf ? q2 : q);
+          if (ph == 0 || (ph == 2 && nb != 0)) { valid = false; break; }
+          if (inside) {
+            if (m < kListCap) L[m] = (uint16_t)(q - b.ustart);
+            ++m;
+            exitq = q2;  // the first record start past the block (the walk's exit)
+          }
+          q = q2;
+        }
+        q = exitq;
+        if (valid) {
+          g = c;
+          x = q;
+          n = m;
+          plaus_list = true;
+        } else {
+          g = kRetry;  // later candidates: k_rec_search (wave per block)
+          n = 0;
+        }
+      }
+    }
+  }
+  if (n > kListCap) atomicOr(overflow, 1u);
+  g_out[i] = g;
+  x_out[i] = x;
+  wcnt[i] = n | (plaus_list ? kListPlausible : 0u);
+}
+
+// Blocks whose first candidate failed (k_rec_walk: g == kRetry): one wave
+// per block tries the later candidates in order (64 positions per step, a
+// wave-uniform walk per candidate), as BAMSplitGuesser tries candidate after
+// candidate; the valid one's records are listed by lane 0.
+template <int MODE>
+__global__ __launch_bounds__(64) void k_rec_search(ChainEnv E, const uint64_t* __restrict__ cand,
+                                                   uint64_t* __restrict__ g_out, uint64_t* __restrict__ x_out,
+                                                   uint32_t* __restrict__ wcnt, uint16_t* __restrict__ list,
+                                                   uint32_t* __restrict__ overflow, uint32_t* __restrict__ searched) {
+  const uint32_t i = blockIdx.x;
+  if (g_out[i] != kRetry) return;
+  const uint32_t lane = lane_id();
+  if (lane == 0) atomicAdd(searched, 1u);  // (hbam_chain_counters)
+  const BlockInfo b = E.blocks[E.k0 + i];
+  const uint64_t bend = b.ustart + b.isize;
+  {  // the walks below are dependent-load chains: pull the block (+ the
+     // lookahead past its end) into L2 first with independent loads
+    uint32_t acc = 0;
+    const uint64_t hi = min(bend + 4096, E.e_inf);
+    for (uint64_t a = (b.ustart & ~127ull) + 128ull * lane; a < hi; a += 128ull * 64) acc += ldu32(E.u, a);
+    if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
+  }
+  uint64_t g = kNone, x = kNone;
+  for (uint64_t c0 = cand[i] + 1; c0 < bend && g == kNone; c0 += 64) {
+    const uint64_t p = c0 + lane;
+    const bool pre = p < bend && cand_prefilter(E, p);
+    uint64_t m = __ballot(pre) ? __ballot(pre && plausible2(E, p)) : 0ull;
+    while (m) {
+      const uint64_t c = c0 + (uint64_t)(__ffsll((long long)m) - 1);
+      m &= m - 1;
+      uint64_t q = c;
+      bool valid = true;
+      while (q < bend) {
+        if (!plausible(E, q)) { valid = false; break; }
+        q += 4 + (uint64_t)(int32_t)ldu32(E.u, q);
+      }
+      if (valid) {
+        uint64_t y = q;
+        for (int k = 0; k < kGuessLookahead; ++k) {
+          if (y == E.e_true || y + 36 > E.e_inf) break;
+          if (!plausible(E, y)) { valid = false; break; }
+          y += 4 + (uint64_t)(int32_t)ldu32(E.u, y);
+        }
+      }
+      if (valid) {
+        g = c;
+        x = q;
+        break;
+      }
+    }
+  }
+  if (lane == 0) {
+    uint32_t n = 0;
+    if (g != kNone) {
+      uint16_t* __restrict__ L = list + (uint64_t)i * kListCap;
+      for (uint64_t q = g; q < bend; q += 4 + (uint64_t)(int32_t)ldu32(E.u, q)) {
+        if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
+        ++n;
+      }
+      if (n > kListCap) atomicOr(overflow, 1u);
+    }
+    g_out[i] = g;
+    x_out[i] = x;
+    wcnt[i] = n | (g != kNone ? kListPlausible : 0u);
+  }
+}
+
+// Parallel link check (in = exclusive max-scan of the guess exits).  Entries
+// where the chain enters a block; a block whose walk does not start there is
+// re-walked from it (force = entry), a stray walk in a pass-through block is
+// dropped (force = kForceEmpty).  A chain that breaks before a block is a
+// hard violation (serial link).
+__global__ void k_rec_linkfix(ChainEnv E, const uint64_t* __restrict__ g, const uint64_t* __restrict__ x,
+                              const uint64_t* __restrict__ in_scan, uint64_t* __restrict__ entry,
+                              uint64_t* __restrict__ force, uint32_t* __restrict__ counters) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t nb = E.k1 - E.k0;
+  if (i >= nb) return;
+  if (i == 0) {
+    entry[0] = E.p0;
+    const BlockInfo b = E.blocks[E.k0];
+    if (x[0] < b.ustart + b.isize) atomicAdd(&counters[0], 1u);  // chain stops in the first block
+    return;
+  }
+  const BlockInfo b = E.blocks[E.k0 + i];
+  const uint64_t bend = b.ustart + b.isize;
+  const uint64_t in = in_scan[i];
+  const uint64_t gi = g[i];
+  uint64_t e = kNone;
+  if (in >= E.q_end) {
+    e = kNone;
+  } else if (in >= bend || b.isize == 0) {
+    if (gi != kNone && x[i] > in) {  // a stray walk would corrupt later in[]
+      force[i] = kForceEmpty;
+      atomicAdd(&counters[1], 1u);
+      atomicAdd(&counters[kChainCtrDropped], 1u);
+    }
+  } else if (in < b.ustart) {
+    atomicAdd(&counters[0], 1u);  // a block before stopped inside itself
+  } else {
+    e = in;
+    if (gi != in) {
+      force[i] = in;
+      atomicAdd(&counters[1], 1u);
+      atomicAdd(&counters[kChainCtrRewalked], 1u);
+    }
+  }
+  entry[i] = e;
+}
+
+// force[] off the serial link's entry[]
+__global__ void k_force_from_entry(const uint64_t* __restrict__ g, const uint64_t* __restrict__ entry, uint32_t nb,
+                                   uint64_t* __restrict__ force) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb) return;
+  const uint64_t e = entry[i], gi = g[i];
+  force[i] = e == gi ? kNone : (e == kNone ? kForceEmpty : e);
+}
+
+// The k_rec_count rules for the listed record at q (one lane): *stop = the
+// block's count ends at this record (*counted: the record itself counts),
+// *s = its status, *nd = bytes past the inflated range the record needs,
+// *long_cigar = its cigar was left to record_invalid_wave.
+template <int MODE>
+__device__ __forceinline__ void check_listed_h(const ChainEnv& E, uint64_t q, uint64_t lim, bool first, bool light,
+                                               bool* stop, bool* counted, int* s, uint64_t* nd, bool* long_cigar,
+                                               const RecHead& h) {
+  const uint64_t avail = E.e_true - q;
+  if (q >= lim) {
+    *stop = true;  // outside the span
+  } else if (light && !dead_near(E, q)) {
+    // all rules pass without reading the record
+  } else if (MODE == kReader) {
+    if (!first && is_dead(E, q)) {
+      *stop = true;  // readInt at an exhausted block + empty block: EOF
+    } else if (avail < 4) {
+      *stop = true;
+    } else if (q + 4 > E.e_inf) {
+      *stop = true;
+      *nd = q + 4;
+    } else {
+      const int32_t bs = (int32_t)h.at(0);
+      if (bs < 32) {
+        *stop = true;
+        *s = kErrFormat;
+      } else if (dead_in_record(E, q, bs) || avail - 4 < (uint64_t)bs) {
+        *stop = true;
+        *s = kErrTrunc;
+      } else if (q + 4 + (uint64_t)bs > E.e_inf) {
+        *stop = true;
+        *nd = q + 4 + (uint64_t)bs;
+      } else {
+        const int32_t ref = (int32_t)h.at(1), nref = (int32_t)h.at(6);
+        if (ref < -1 || ref >= E.n_ref || nref < -1 || nref >= E.n_ref) {
+          *stop = true;
+          *s = kErrArg;
+        } else if (E.validate && record_invalid_h(E, q, bs, E.validate == 2, long_cigar, h)) {
+          *stop = true;
+          *s = kErrFormat;
+        }
+      }
+    }
+  } else {
+    if (is_dead(E, q)) {
+      *stop = true;
+    } else if (avail < 4) {
+      *stop = true;
+      if (avail > 0) *s = kErrIO;  // "less than 4 bytes long"
+    } else if (q + 4 > E.e_inf) {
+      *stop = true;
+      *nd = q + 4;
+    } else {
+      const int32_t bs = (int32_t)h.at(0);
+      if (bs > 0 && ((uint64_t)bs > avail - 4 || is_dead(E, q + 4))) {
+        *stop = true;
+        *counted = true;
+        *s = kErrIO;  // "Skip failed"
+      }
+    }
+  }
+}
+// Record check and output in one pass (the list path of decode_span_pos):
+// the record rules, the long-cigar validation and the output, one wave per
+// block, so a block's records are read from HBM once after inflate and
+// written out while they are in L2.  A block writes its records at base[i],
+// the exclusive scan of the lists' counts: the true offsets for every block
+// up to the first one that stops early, since every block before it keeps
+// its whole list.  A stop ends the reader's iteration (a failure, EOF at an
+// empty block, the end of the stream or of the span) and the indexer's, so
+// the span's records are exactly those up to the first stop, and what later
+// blocks write lies past them.  The launch reports:
+//   bad[0]   min over blocks that stop early or fail of (i << 40 | base[i] +
+//            count): the first such block and the records up to its stop
+//   flags[0] the first failing block (its status is the span's when it is
+//            the first stop)
+//   cnt[] / err[] per block, need = the bytes a stopped record needs past
+//            the inflated range.
+constexpr int kBadShift = 40;
+
+// (4 / 6 / 8 waves per SIMD: 1.116 / 1.065 / 1.052 ms per C2 pass,
+// profiles/r06_late/variants_check_out_waves.log)
+template <int MODE, bool DECODE>
+__global__ __launch_bounds__(64, 6) void k_rec_check_out(ChainEnv E, const uint64_t* __restrict__ entry,
+                                                         const uint32_t* __restrict__ wcnt,
+                                                         const uint16_t* __restrict__ list,
+                                                         const uint64_t* __restrict__ base, uint32_t* __restrict__ cnt,
+                                                         int32_t* __restrict__ err,
+                                                         unsigned long long* __restrict__ need,
+                                                         unsigned long long* __restrict__ bad,
+                                                         uint32_t* __restrict__ flags, uint64_t* __restrict__ rec_pos,
+                                                         uint64_t* __restrict__ rec_voff, Columns col, uint64_t cap) {
+  const uint32_t lane = lane_id();
+  const uint32_t i = blockIdx.x;
+  const uint64_t e = entry[i];
+  const BlockInfo b = E.blocks[E.k0 + i];
+  const uint16_t* __restrict__ L = list + (uint64_t)i * kListCap;
+  const uint64_t lim = min(b.ustart + b.isize, E.q_end);
+  const uint32_t wc = wcnt[i];
+  const uint32_t listed = e == kNone ? 0u : min(wc & kListCountMask, kListCap);
+  // (check_block's rules) a plausible() list on fully inflated data already
+  // satisfies every rule that reads the record
+  const bool light = (wc & kListPlausible) && E.e_inf == E.e_true && (MODE != kReader || E.validate == 0);
+  const uint64_t o0 = base[i];
+  uint32_t count = listed;
+  int st = kOk;
+  uint64_t nd = 0;
+  // 64 records at a time: check them, validate their long cigars, and write
+  // the ones before the first stop while their lines are still in L1/L2 (a
+  // whole block checked before any output re-fetched every line: 5.9 GB per
+  // C2 pass)
+  for (uint32_t r0 = 0; r0 < listed; r0 += 64) {
+    const uint32_t r = r0 + lane;
+    const uint64_t q = r < listed ? b.ustart + L[r] : 0;
+    bool stop = false, counted = false, long_cigar = false;
+    int s = kOk;
+    uint64_t x = 0;
+    // the record's head is loaded once for the checks and the output (three
+    // passes over it re-fetched its lines from HBM: 5.3 GB per C2 pass)
+    RecHead h{};
+    if (r < listed) {
+      h = load_head(E.u, q);
+      check_listed_h<MODE>(E, q, lim, r == 0 && q == E.p0, light, &stop, &counted, &s, &x, &long_cigar, h);
+    }
+    uint32_t m = min(64u, listed - r0);  // records of this chunk that stand
+    const uint64_t sm = __ballot(stop);
+    bool halt = sm != 0;  // the block's count ends in this chunk
+    if (sm) {
+      const uint32_t f = (uint32_t)__ffsll((long long)sm) - 1;
+      m = f + (uint32_t)__shfl((int)counted, (int)f, 64);
+      st = __shfl(s, (int)f, 64);
+      nd = shfl_u64(x, f);
+    }
+    if (MODE == kReader) {
+      // cigars longer than kWaveCigarOps before the stop, a wave each in order
+      // (k_rec_check_long): the first invalid one becomes the stop
+      const bool lg = lane < m && long_cigar;
+      for (uint64_t wm = __ballot(lg); wm; wm &= wm - 1) {
+        const uint32_t src = (uint32_t)__ffsll((long long)wm) - 1;
+        const uint64_t qq = shfl_u64(q, src);
+        if (record_invalid_wave(E, qq, (int32_t)ldu32(E.u, qq), E.validate == 2)) {
+          m = src;
+          st = kErrFormat;
+          nd = 0;
+          halt = true;
+          break;
+        }
+      }
+    }
+    if (lane < m) {
+      const uint64_t o = o0 + r;
+      if (o < cap) {  // (sized from the lists' counts: always)
+        rec_pos[o] = q;
+        rec_voff[o] = (b.coff << 16) | (q - b.ustart);
+        if (DECODE) decode_record_h(E.u, q, o, col, h);
+      }
+    }
+    if (halt) {
+      count = r0 + m;
+      break;
+    }
+  }
+  if (lane == 0) {
+    if (nd) atomicMax(need, (unsigned long long)nd);
+    cnt[i] = count;
+    err[i] = st;
+    if (count < listed || st != kOk)
+      atomicMin(bad, ((unsigned long long)i << kBadShift) | (unsigned long long)(o0 + count));
+    if (st != kOk) atomicMin(&flags[0], i);
+    // (no per-block atomic on a shared word here: 52 K of them on one address
+    // serialize across the XCDs; k_records_after answers for the rare stop)
+  }
+}
+
+// *flag = 1 when a block after block k has records (a span cut at an early
+// stop dropped them: a diagnostic, hbam_pipeline_counters)
+__global__ void k_records_after(const uint32_t* __restrict__ cnt, uint32_t nb, uint32_t k, uint32_t* __restrict__ flag) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > k && i < nb && cnt[i]) *flag = 1u;
+}
+hipError_t launch_records_after(const uint32_t* cnt, uint32_t nb, uint32_t k, uint32_t* flag, hipStream_t s) {
+  hipLaunchKernelGGL(k_records_after, dim3((nb + 255) / 256), dim3(256), 0, s, cnt, nb, k, flag);
+  return hipGetLastError();
+}
+
+// first block (index) whose status is non-zero -> *first (atomicMin), status -> code[]
+__global__ void k_first_error_hout(const HuffOut* __restrict__ hout, uint32_t b0, uint32_t nb,
+                                   uint32_t* __restrict__ first) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb && hout[b0 + i].status != kOk) atomicMin(first, i);
+}
+__global__ void k_first_error_i32(const int32_t* __restrict__ err, uint32_t nb, uint32_t* __restrict__ first) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb && err[i] != kOk) atomicMin(first, i);
+}
+// zero the counts of blocks after `cut` (the first failing block)
+__global__ void k_truncate_counts(uint32_t* __restrict__ cnt, uint32_t nb, const uint32_t* __restrict__ cut) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb && i > *cut) cnt[i] = 0;
+}
+
+// cnt[i] = the records block i's list holds (0 off the chain): the
+// optimistic output counts k_rec_check_out's offsets are scanned from
+__global__ void k_list_counts(const uint64_t* __restrict__ entry, const uint32_t* __restrict__ wcnt, uint32_t nb,
+                              uint32_t* __restrict__ cnt) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nb) cnt[i] = entry[i] != kNone ? min(wcnt[i] & kListCountMask, kListCap) : 0u;
+}
+
+// ---- host launch wrappers (hbam_launch.h)
+static ChainEnv chain_env(const ChainArgs& a) {
+  ChainEnv E;
+  E.u = a.u;
+  E.blocks = a.blocks;
+  E.e_inf = a.e_inf;
+  E.e_true = a.e_true;
+  E.p0 = a.p0;
+  E.q_end = a.q_end;
+  E.dead = a.dead;
+  E.ndead = a.ndead;
+  E.n_ref = a.n_ref;
+  E.k0 = a.k0;
+  E.k1 = a.k1;
+  E.validate = a.validate;
+  E.ref_len = a.ref_len;
+  return E;
+}
+
+// f(m) with the run-time mode as the compile-time constant decltype(m)::value
+template <typename F>
+static void with_mode(int mode, F f) {
+  if (mode == kReader) f(std::integral_constant<int, kReader>());
+  else f(std::integral_constant<int, kIndexer>());
+}
+
+hipError_t launch_chain(const ChainArgs& a, int mode, int stage, hipStream_t s) {
+  const ChainEnv E = chain_env(a);
+  const uint32_t nb = a.k1 - a.k0;
+  if (nb == 0) return hipSuccess;
+  const unsigned tb = 64, gb = (nb + tb - 1) / tb;
+  switch (stage) {
+    case kStageSerialLink:
+      with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(k_rec_link<decltype(m)::value>, dim3(1), dim3(256), 0, s, E, a.g, a.x, a.entry, a.summary);
+      });
+      break;
+    case kStageCount:
+      with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(k_rec_count<decltype(m)::value>, dim3(gb), dim3(tb), 0, s, E, a.entry, a.cnt, a.err, a.need);
+      });
+      break;
+    case kStageEmit:
+      with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(k_rec_emit<decltype(m)::value>, dim3(gb), dim3(tb), 0, s, E, a.entry, a.cnt, a.base,
+                           a.rec_pos, a.rec_voff);
+      });
+      break;
+    case kStageWalk:  // candidates + walks
+      with_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        hipLaunchKernelGGL(k_rec_cand<M>, dim3(nb), dim3(64), 0, s, E, a.cand);
+        hipLaunchKernelGGL(k_rec_walk<M>, dim3((nb + 255) / 256), dim3(256), 0, s, E, a.cand, nullptr, a.g, a.x,
+                           a.wcnt, a.list, a.counters + 2, false);
+        hipLaunchKernelGGL(k_rec_search<M>, dim3(nb), dim3(64), 0, s, E, a.cand, a.g, a.x, a.wcnt, a.list,
+                           a.counters + 2, a.counters + kChainCtrSearched);
+      });
+      break;
+    case kStageLinkCheck: {  // y, exclusive max-scan, check with re-walk requests
+      hipError_t e = hipMemsetAsync(a.force, 0xff, (size_t)nb * 8, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_rec_link_y, dim3(gb), dim3(tb), 0, s, a.g, a.x, nb, a.x2);
+      size_t sb = a.scan_bytes;
+      e = hipcub::DeviceScan::ExclusiveScan(a.scan_tmp, sb, a.x2, a.base, hipcub::Max(), (uint64_t)0, (int)nb, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(k_rec_linkfix, dim3(gb), dim3(tb), 0, s, E, a.g, a.x, a.base, a.entry, a.force, a.counters);
+      break;
+    }
+    case kStageRewalk:       // re-walk the requested blocks (entries validated)
+    case kStageRewalkAll: {  // force off the serial link's (exact) entry[], then re-walk
+      const bool validate = stage == kStageRewalk;
+      if (stage == kStageRewalkAll) hipLaunchKernelGGL(k_force_from_entry, dim3(gb), dim3(tb), 0, s, a.g, a.entry, nb, a.force);
+      with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(k_rec_walk<decltype(m)::value>, dim3((nb + 255) / 256), dim3(256), 0, s, E, a.cand, a.force,
+                           a.g, a.x, a.wcnt, a.list, a.counters + 2, validate);
+      });
+      break;
+    }
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_list_counts(const ChainArgs& a, hipStream_t s) {
+  const uint32_t nb = a.k1 - a.k0;
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_list_counts, dim3((nb + 255) / 256), dim3(256), 0, s, a.entry, a.wcnt, nb, a.cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_rec_check_out(const ChainArgs& a, int mode, bool decode, const Columns& col, uint64_t cap,
+                                hipStream_t s) {
+  static_assert(kBadShift == kFusedBadShift, "hbam_launch.h kFusedBadShift");
+  const ChainEnv E = chain_env(a);
+  const uint32_t nb = a.k1 - a.k0;
+  if (nb == 0) return hipSuccess;
+  unsigned long long* need = a.need;
+  unsigned long long* bad = reinterpret_cast<unsigned long long*>(a.fuse_bad);
+#define HBAM_CO(M, D)                                                                                            \
+  hipLaunchKernelGGL((k_rec_check_out<M, D>), dim3(nb), dim3(64), 0, s, E, a.entry, a.wcnt, a.list, a.base, a.cnt, \
+                     a.err, need, bad, a.fuse_flags, a.rec_pos, a.rec_voff, col, cap)
+  if (mode == kReader && decode) HBAM_CO(kReader, true);
+  else if (mode == kReader) HBAM_CO(kReader, false);
+  else HBAM_CO(kIndexer, false);
+#undef HBAM_CO
+  return hipGetLastError();
+}
+
+hipError_t link_scan_bytes(uint32_t nb, size_t* bytes) {
+  uint64_t* p = nullptr;
+  return hipcub::DeviceScan::ExclusiveScan(nullptr, *bytes, p, p, hipcub::Max(), (uint64_t)0, (int)nb, (hipStream_t)0);
+}
+
+hipError_t launch_first_error_hout(const HuffOut* hout, uint32_t b0, uint32_t nb, uint32_t* first, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_first_error_hout, dim3((nb + 255) / 256), dim3(256), 0, s, hout, b0, nb, first);
+  return hipGetLastError();
+}
+hipError_t launch_first_error_i32(const int32_t* err, uint32_t nb, uint32_t* first, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_first_error_i32, dim3((nb + 255) / 256), dim3(256), 0, s, err, nb, first);
+  return hipGetLastError();
+}
+hipError_t launch_truncate_counts(uint32_t* cnt, uint32_t nb, const uint32_t* cut, hipStream_t s) {
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_truncate_counts, dim3((nb + 255) / 256), dim3(256), 0, s, cnt, nb, cut);
+  return hipGetLastError();
+}
+
+}  // namespace hbam

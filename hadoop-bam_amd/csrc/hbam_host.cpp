@@ -1,7 +1,7 @@
 // hbam_host.cpp -- C++ mirror of org.seqdoop.hadoop_bam's BAM read path
 // classes on top of the gfx950 pipeline.  Host code here plans windows,
 // parses the header and copies results; every per-record / per-byte loop of
-// the hot path runs in hbam_kernels.hip.
+// the hot path runs in the .hip kernel files (hbam_launch.h lists them).
 #include "hbam_mem.h"
 #include "hbam_host.h"
 

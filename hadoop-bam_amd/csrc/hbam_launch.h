@@ -58,7 +58,7 @@ enum ChainStage : int {
   kStageRewalk = 7,      // re-walk the requested blocks (entries validated)
   kStageRewalkAll = 8,   // re-walk every block off the serial link's entry[]
 };
-
+// ---- hbam_locate.hip: BGZF block discovery
 // candidates in [lo, hi); file + buf_base is the (aligned) device buffer start
 hipError_t launch_bgzf_scan(const uint8_t* file, uint64_t buf_base, uint64_t lo, uint64_t hi, uint64_t* cand,
                             uint32_t cap, uint32_t* count, hipStream_t s);
@@ -84,6 +84,7 @@ hipError_t sort_u64(void* tmp, size_t* tmp_bytes, uint64_t* keys_in, uint64_t* k
                     hipStream_t s);
 hipError_t scan_u32_to_u64(void* tmp, size_t* tmp_bytes, const uint32_t* in, uint64_t* out, uint32_t n,
                            hipStream_t s);
+// ---- hbam_kernels.hip: inflate phase A
 // inflate phase A in two launches: the first DEFLATE block's header + tables
 // of every block of a chunk (k_huff_tables), then the decode reading them
 // (round 0: the header at each block's start; round r > 0: where decode
@@ -107,8 +108,10 @@ hipError_t launch_inflate_huff_prebuilt(const uint8_t* file, const BlockInfo* bl
 hipError_t huff_lean_occupancy(int* workgroups_per_cu);
 // the same for the narrow instance, and the bytes of window its stage holds
 hipError_t huff_narrow_occupancy(int* workgroups_per_cu, uint32_t* stage_cap_bytes);
+// ---- hbam_inflate_lz77.hip: inflate phase B
 hipError_t launch_inflate_lz77(const BlockInfo* blocks, uint32_t b0, uint32_t nb, uint64_t chunk_ustart,
                                const uint32_t* tokens, const HuffOut* hout, uint8_t* u, hipStream_t s);
+// ---- hbam_chain.hip: the record chain
 hipError_t launch_chain(const ChainArgs& a, int mode, int stage, hipStream_t s);
 // a.cnt[i] = the records block i's list holds (0 off the chain): scanned into
 // a.base, the offsets launch_rec_check_out writes at
@@ -121,12 +124,13 @@ hipError_t launch_rec_check_out(const ChainArgs& a, int mode, bool decode, const
                                 hipStream_t s);
 constexpr int kFusedBadShift = 40;
 hipError_t link_scan_bytes(uint32_t nb, size_t* bytes);
-hipError_t launch_rec_decode(const uint8_t* u, const uint64_t* rec_pos, uint64_t n, const Columns& col,
-                             hipStream_t s);
 hipError_t launch_first_error_hout(const HuffOut* hout, uint32_t b0, uint32_t nb, uint32_t* first, hipStream_t s);
 hipError_t launch_records_after(const uint32_t* cnt, uint32_t nb, uint32_t k, uint32_t* flag, hipStream_t s);
 hipError_t launch_first_error_i32(const int32_t* err, uint32_t nb, uint32_t* first, hipStream_t s);
 hipError_t launch_truncate_counts(uint32_t* cnt, uint32_t nb, const uint32_t* cut, hipStream_t s);
+// ---- hbam_records.hip: record output and the SAMRecordWritable codec
+hipError_t launch_rec_decode(const uint8_t* u, const uint64_t* rec_pos, uint64_t n, const Columns& col,
+                             hipStream_t s);
 // .splitting-bai entries of records with global ordinals o0 .. o0+n-1
 // (ordinals k*g - 1): ent[j] for the j-th such ordinal of the span
 hipError_t launch_sbi_emit(const uint64_t* voff, uint64_t n, uint32_t g, uint64_t o0, uint64_t* ent, hipStream_t s);
@@ -164,6 +168,10 @@ hipError_t launch_long_hash(const uint8_t* u, const uint64_t* rec_pos, const Col
 // (16 B-aligned, room for nbytes rounded up to 16) + bin patches (refID < 0)
 hipError_t launch_wr_encode(const uint8_t* u, uint64_t p0, uint64_t nbytes, const uint64_t* rec_pos,
                             const int32_t* ref_id, const uint16_t* bin, uint64_t n, uint8_t* dst, hipStream_t s);
+// SAMRecordWritable.readFields of n framed values; *bad = min((i << 8) | status)
+hipError_t launch_wr_decode(const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n, const Columns& col,
+                            uint64_t* rec_pos, unsigned long long* bad, hipStream_t s);
+// ---- hbam_sort.hip
 // Sorted SAMRecordWritable.write of a span's records (hbam_sort.hip), n < 2^31 - 1.
 // order: kSortKey = ascending signed key, kSortCoordinate = ascending
 // (uint32 refID, pos + 1); both stable.
@@ -185,6 +193,7 @@ hipError_t launch_sort_gather(const uint8_t* u, const uint64_t* rec_pos, const i
 // k_sort_words alone: the sort words, encoded lengths and iota of n decoded records
 hipError_t launch_sort_words(const Columns& col, uint64_t n, int order, uint64_t* word, uint32_t* len, uint32_t* iota,
                              hipStream_t s);
+// ---- hbam_samtext.hip
 // SAM text of a span's records (hbam_samtext.hip), n < 2^31 - 1: one line per
 // record in batch order.  The reference names: ref_bytes back to back, name r =
 // [ref_off[r], ref_off[r + 1]) (n_ref + 1 u32).
@@ -205,6 +214,7 @@ hipError_t launch_sam_write(const uint8_t* u, const uint64_t* rec_pos, const Col
                             const uint32_t* ref_off, const uint8_t* ref_bytes, int32_t n_ref,
                             const uint32_t* head_len, const uint64_t* doff, uint64_t total, uint8_t* dst,
                             hipStream_t s);
+// ---- hbam_names.hip
 // Queryname order (hbam_names.hip): the name = name_len bytes at base +
 // name_pos, zero-extended and compared as unsigned bytes, then the tie word
 // (2 * mate rank + secondary/supplementary, from the flag), then the input
@@ -246,6 +256,7 @@ hipError_t launch_name_starts(void* tmp, size_t tmp_bytes, const uint8_t* name_l
 // the names copied back to back: dst[dst_base + at[i] ..) = the name at src + name_pos[i]; name_pos[i] = dst_base + at[i]
 hipError_t launch_name_pack(const uint8_t* src, uint64_t* name_pos, const uint8_t* name_len, const uint64_t* at,
                             uint64_t n, uint8_t* dst, uint64_t dst_base, hipStream_t s);
+// ---- hbam_merge.hip
 // Merge of k sorted runs of SAMRecordWritable encodings (hbam_merge.hip), total
 // records n < 2^31 - 1.  A record's global index is run-major: run_base[r] + i
 // (run_base: k + 1 u64).  Every run's n_r + 1 offsets lie back to back in one
@@ -285,8 +296,5 @@ hipError_t launch_merge_src(const uint32_t* perm, const uint64_t* doff, uint64_t
 // total rounded up to 16, u is readable 16 bytes past its last record
 hipError_t launch_merge_gather(const uint8_t* u, const uint64_t* src_pos, const uint64_t* doff, uint64_t n,
                                uint64_t dbase, uint64_t total, uint8_t* dst, hipStream_t s);
-// SAMRecordWritable.readFields of n framed values; *bad = min((i << 8) | status)
-hipError_t launch_wr_decode(const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n, const Columns& col,
-                            uint64_t* rec_pos, unsigned long long* bad, hipStream_t s);
 
 }  // namespace hbam

@@ -7,7 +7,7 @@
 // record that runs past its last block is not truncated, it is left for the
 // next window (BamFile in hbam_host.h moves windows along a span and carries
 // the next record's position across).  All compute runs in the gfx950
-// kernels of hbam_kernels.hip; the host sizes buffers, launches and reads
+// kernels behind hbam_launch.h; the host sizes buffers, launches and reads
 // back counters.  There is no CPU fallback: any HIP failure is an error
 // returned to the caller.
 #pragma once

@@ -165,21 +165,7 @@ __global__ __launch_bounds__(kQueryThreads) void k_query_gather(Columns s, uint6
   src_off[j] = s.rest_off[i];
 }
 
-// 16 bytes starting sh bytes into the 32-byte pair (a, b); as hbam_kernels.hip
-__device__ __forceinline__ uint4 shift16(const uint4 a, const uint4 b, uint32_t sh) {
-  const uint32_t r = sh & 3;
-  uint32_t w0, w1, w2, w3, w4;
-  switch (sh >> 2) {
-    case 0: w0 = a.x; w1 = a.y; w2 = a.z; w3 = a.w; w4 = b.x; break;
-    case 1: w0 = a.y; w1 = a.z; w2 = a.w; w3 = b.x; w4 = b.y; break;
-    case 2: w0 = a.z; w1 = a.w; w2 = b.x; w3 = b.y; w4 = b.z; break;
-    default: w0 = a.w; w1 = b.x; w2 = b.y; w3 = b.z; w4 = b.w; break;
-  }
-  return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, r), __builtin_amdgcn_alignbyte(w2, w1, r),
-                    __builtin_amdgcn_alignbyte(w3, w2, r), __builtin_amdgcn_alignbyte(w4, w3, r));
-}
-
-// The kept records' rests back to back.  k_pack_rests computes a record's
+// The kept records' rests back to back.  k_pack_rests (hbam_records.hip) computes a record's
 // source from its slot (contiguous records); kept records are scattered, so
 // here a workgroup takes 256 kept records with their destination (cp) and
 // source (sp) offsets in LDS and writes 16-byte output chunks: a shifted 16 B

@@ -18,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "hbam_dev_util.h"  // shift16
 #include "hbam_launch.h"
 
 namespace hbam {
@@ -50,21 +51,6 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_lens(const uint32_t* __re
   const uint64_t j = (uint64_t)blockIdx.x * kSortThreads + threadIdx.x;
   if (j < n) slen[j] = len[perm[j]];
   else if (j == n) slen[j] = 0;
-}
-
-// 16 bytes starting sh bytes into the 32-byte pair (a, b) (k_pack_rests's; sh
-// differs from lane to lane here: the four cases are selects, not a table)
-__device__ __forceinline__ uint4 shift16(const uint4 a, const uint4 b, uint32_t sh) {
-  const uint32_t r = sh & 3;
-  uint32_t w0, w1, w2, w3, w4;
-  switch (sh >> 2) {
-    case 0: w0 = a.x; w1 = a.y; w2 = a.z; w3 = a.w; w4 = b.x; break;
-    case 1: w0 = a.y; w1 = a.z; w2 = a.w; w3 = b.x; w4 = b.y; break;
-    case 2: w0 = a.z; w1 = a.w; w2 = b.x; w3 = b.y; w4 = b.z; break;
-    default: w0 = a.w; w1 = b.x; w2 = b.y; w3 = b.z; w4 = b.w; break;
-  }
-  return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, r), __builtin_amdgcn_alignbyte(w2, w1, r),
-                    __builtin_amdgcn_alignbyte(w3, w2, r), __builtin_amdgcn_alignbyte(w4, w3, r));
 }
 
 // dst[doff[j], doff[j + 1]) = the bytes of record perm[j] (u + rec_pos[perm[j]]),
@@ -140,6 +126,7 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_gather(const uint8_t* __r
       const uint32_t sh = (uint32_t)(src & 15);
       const uint4* q = reinterpret_cast<const uint4*>(u + (src & ~15ull));
       uint4 v = q[0];
+      // (sh differs from lane to lane here: shift16's four cases are selects, not a table)
       if (sh) v = shift16(v, q[1], sh);
       // indexBin = 0: record bytes 14-15, at chunk byte rel (-1: byte 15 alone is chunk byte 0)
       const int64_t rel = (int64_t)(ro + 14) - (int64_t)c;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development aid: per-step clock probes in k_inflate_lz77 (phase B).
-`apply` saves the clean hbam_kernels.hip / hbam_pipeline.cpp / hbam_launch.h
+`apply` saves the clean hbam_inflate_lz77.hip / hbam_pipeline.cpp / hbam_launch.h
 under /tmp and writes probed copies (cycles per step summed over blocks,
 printed by the pipeline after each inflate when HBAM_LZ_STATS is set);
 `revert` restores them.  Build the probed library as a variant:
@@ -9,7 +9,7 @@ printed by the pipeline after each inflate when HBAM_LZ_STATS is set);
 import shutil
 import sys
 
-K = "hadoop-bam_amd/csrc/hbam_kernels.hip"
+K = "hadoop-bam_amd/csrc/hbam_inflate_lz77.hip"
 PL = "hadoop-bam_amd/csrc/hbam_pipeline.cpp"
 LH = "hadoop-bam_amd/csrc/hbam_launch.h"
 

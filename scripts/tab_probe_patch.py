@@ -42,7 +42,7 @@ KEDITS = [  # (anchor, text, insert after the anchor?)
      "        TBP(6);\n", True),
     ("        ti = HuffTableInfo{0u, b0pos + 8u * sb, fin, est};\n",
      "        TBP(7);\n        wave_sync();\n        TBP(9);\n        if (lane == 0 && (blockIdx.x & 63) == 0) atomicAdd(&g_tab_probe[8], 1ull);\n", True),
-    ("hipError_t launch_inflate_lz77(",
+    ("hipError_t launch_huff_tables(",
      "hipError_t tab_probe_read(unsigned long long* t) { return hipMemcpyFromSymbol(t, HIP_SYMBOL(g_tab_probe), 128); }\n",
      False),
 ]

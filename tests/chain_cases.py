@@ -22,7 +22,7 @@ and plausible() rejects: the guess of their block fails, and only the link
 step can put them on the chain.
 
 plausible / plausible2 / chain_step / guess_walk / block_guess restate the
-device functions of hbam_kernels.hip in plain Python, with e_inf (the end of
+device functions of hbam_chain.hip in plain Python, with e_inf (the end of
 the inflated range) as a parameter.  They are used only to assert that an
 input has the property its case is named for, never for expected outputs.
 
