@@ -101,8 +101,12 @@ int BaiBuilder::add_window(BamFile& f, const SpanDev& s, std::string* err) {
   BCHK(hbam::launch_bai_classify(u, s.col, n, t, w, state_.p, st));
   BCHK(hbam::launch_bai_link(tmp_.p, tb, s.col, n, carry_key_, carry_sk_, t, w, state_.p, st));
   uint64_t v[hbam::kBaiStateWords];
-  BCHK(p.rb(v, state_.p, sizeof v, st));
-  BCHK(p.rb_sync(st));
+  hipError_t e = p.rb(v, state_.p, sizeof v, st);
+  if (e == hipSuccess) e = p.rb_sync(st);
+  if (e != hipSuccess) {
+    p.rb_cancel();  // v is a local: the queue must not keep its address
+    return hip_err(e, "read-back of the index state", err);
+  }
   if (v[hbam::kBaiErr] != ~0ull) {
     const std::string rec = "record " + std::to_string(records_ + (v[hbam::kBaiErr] >> 2));
     switch ((int)(v[hbam::kBaiErr] & 3)) {

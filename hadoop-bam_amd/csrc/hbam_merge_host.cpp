@@ -45,6 +45,7 @@ int Merger::fail(int code, const std::string& msg) {
 int Merger::hip_check(hipError_t e, const char* what) {
   if (e == hipSuccess) return kOk;
   err_ = std::string(what) + ": " + hipGetErrorString(e);
+  p_.rb_cancel();  // the failing call returns before its rb_sync: no queued read outlives its frame
   return kErrDevice;
 }
 

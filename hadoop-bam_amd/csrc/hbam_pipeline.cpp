@@ -29,6 +29,17 @@ constexpr int kMaxLinkFix = 4;        // re-walk rounds before the serial link
 constexpr int kMaxFreeStarts = 64;    // header candidates tried by a free-start locate
 // e_true of an open window: records may run past its last block
 constexpr uint64_t kOpenEnd = 1ull << 62;
+constexpr uint32_t kNoBlock = 0xffffffffu;  // "no failing block" of the first-error kernels
+// the next `bytes` of a buffer carved up in 16 B-aligned pieces
+uint8_t* take16(uint8_t** p, uint64_t bytes) {
+  uint8_t* r = *p;
+  *p += (bytes + 15) & ~15ull;
+  return r;
+}
+bool cursor_trace() {
+  static const bool tr = getenv("HBAM_CURSOR_TRACE") != nullptr;
+  return tr;
+}
 }  // namespace
 
 hipError_t create_stream(hipStream_t* s, StreamLevel level) {
@@ -103,10 +114,11 @@ int Pipeline::fail(int code, const std::string& msg) {
 int Pipeline::hip_check(hipError_t e, const char* what) {
   if (e == hipSuccess) return kOk;
   err_ = std::string(what) + ": " + hipGetErrorString(e);
+  rb_cancel();  // the failing call returns before its rb_sync: no queued read outlives its frame
   return kErrDevice;
 }
 
-#define HIPCHK(expr)                                   \
+#define HIPCHK(expr)                                  \
   do {                                                 \
     int _rc = hip_check((expr), #expr);                \
     if (_rc != kOk) return _rc;                        \
@@ -133,7 +145,7 @@ int Pipeline::load_from(const HostSource& src, uint64_t src_off, uint64_t len, u
     if (rc != kOk) err_ = e;
     return rc;
   };
-  static const bool tr = getenv("HBAM_CURSOR_TRACE") != nullptr;
+  const bool tr = cursor_trace();
   const auto t0 = std::chrono::steady_clock::now();
   // the prefix of [base, base + len) that the window in place already holds
   uint64_t keep = 0;
@@ -217,6 +229,12 @@ hipError_t Pipeline::rb_sync(hipStream_t s) {
   rb_used_ = 0;
   rb_stream_ = nullptr;
   return hipSuccess;
+}
+
+void Pipeline::rb_cancel() {
+  rb_items_.clear();
+  rb_used_ = 0;
+  rb_stream_ = nullptr;
 }
 
 int Pipeline::copy_from_host(uint8_t* dst, const HostSource& src, uint64_t off, uint64_t len) {
@@ -928,19 +946,63 @@ int Pipeline::decode_span(uint64_t vstart, uint64_t vend, ChainMode mode, bool d
   return decode_span_pos((uint64_t)sp, vend, mode, decode, out);
 }
 
+// One record pass over a span: the steps (below, in call order) share a
+// SpanPass; the map of the steps and their host waits is in hbam_pipeline.h.
 int Pipeline::decode_span_pos(uint64_t p0, uint64_t vend, ChainMode mode, bool decode, SpanDev* out) {
   HIPCHK(hipSetDevice(device_));
   *out = SpanDev();
+  SpanPass s;
+  if (!span_range(p0, vend, mode, decode, out, s)) return kOk;  // an empty span
+  if (timing) HIPCHK(hipEventRecord(ev_[0], stream_));
+  for (int it = 0;; ++it) {
+    if (it >= kMaxChainIters) return fail(kErrState, "record chain did not converge");
+    after_stop_pending_ = false;  // (only the last round's stop counts)
+    int rc = span_inflate(s);
+    if (rc == kOk) rc = span_scratch(s);
+    if (rc == kOk) rc = span_link(s);
+    if (rc == kOk) rc = s.lists ? span_check_out(s) : span_count(s);
+    if (rc != kOk) return rc;
+    if (!span_grow(s)) break;
+  }
+  int rc = s.lists ? span_status(s, out) : span_emit_walks(s, out);
+  if (rc != kOk) return rc;
+  out->n = s.total;
+  out->rec_pos = rec_pos_.p;
+  out->rec_voff = rec_voff_.p;
+  if (s.dec) out->col = s.c;
+  if (!s.tail_done) {  // (else done and read with k_rec_check_out's verdict; then total == bound)
+    if ((rc = span_tail(s, s.total, false)) != kOk) return rc;
+    if (timing) HIPCHK(hipEventRecord(ev_[2], stream_));
+    HIPCHK(rb_sync(stream_));
+  }
+  out->next_pos = s.next;
+  out->first_voff = s.voff[0];
+  out->last_voff = s.voff[1];
+  if (after_stop_pending_ && after_stop_flag_) ++records_after_stop_;
+  after_stop_pending_ = false;
+  after_stop_flag_ = 0;
+  if (timing) span_times(s);
+  return kOk;
+}
+
+// Range setup.  Reads the block table.  Leaves in s: mode, dec, ahead, nblk,
+// [k0, k1) = the blocks that hold [p0, q_end), inf_end = the inflate's end
+// (two blocks further), and the ChainArgs fields that no round changes; in
+// *out: p0, q_end and next_pos = p0.  Queues nothing.  false: the span is empty.
+bool Pipeline::span_range(uint64_t p0, uint64_t vend, ChainMode mode, bool decode, SpanDev* out, SpanPass& s) {
   const uint64_t q_end = q_end_of(vend);
   out->p0 = p0;
   out->q_end = q_end;
   out->next_pos = p0;
-  const uint32_t nblk = (uint32_t)hblocks_.size();
-  if (p0 >= q_end || p0 >= total_u_) return kOk;
-  const uint32_t k0 = block_containing(p0);
-  uint32_t k1 = std::min(nblk, block_containing(std::min(q_end, total_u_) - 1) + 1);
-  uint32_t inf_end = std::min(nblk, k1 + 2);
-  ChainArgs a{};
+  if (p0 >= q_end || p0 >= total_u_) return false;
+  s.mode = mode;
+  s.dec = decode && mode == kReader;
+  s.ahead = !timing;
+  s.nblk = (uint32_t)hblocks_.size();
+  s.k0 = block_containing(p0);
+  s.k1 = std::min(s.nblk, block_containing(std::min(q_end, total_u_) - 1) + 1);
+  s.inf_end = std::min(s.nblk, s.k1 + 2);
+  ChainArgs& a = s.a;
   a.blocks = dblocks_.p;
   a.e_true = at_eof_ ? total_u_ : kOpenEnd;
   a.p0 = p0;
@@ -948,372 +1010,394 @@ int Pipeline::decode_span_pos(uint64_t p0, uint64_t vend, ChainMode mode, bool d
   a.dead = dead_.p;
   a.ndead = ndead_;
   a.n_ref = n_ref_;
-  a.k0 = k0;
+  a.k0 = s.k0;
   a.validate = mode != kReader ? 0 : stringency_ == kStrict ? 2 : stringency_ == kLenient ? 1 : 0;
   a.ref_len = n_ref_len_ == (uint32_t)std::max(n_ref_, 0) && n_ref_len_ ? ref_len_.p : nullptr;
-  if (timing) HIPCHK(hipEventRecord(ev_[0], stream_));
-  float infl_ms = 0, huff_ms = 0, lz_ms = 0, tab_ms = 0;
-  bool lists = true;  // chain v2 lists hold every record start (no overflow)
-  const bool dec = decode && mode == kReader;
-  Columns c{};
-  // the list path: check + output in one launch (k_rec_check_out); its results
-  bool fused = false;
-  uint64_t fused_total = 0;
-  uint32_t fused_first = 0xffffffffu;
-  // the span's tail (deferred long keys + the next record's start) queued
-  // with k_rec_check_out, gated on its verdict, read back with it
-  bool spec_tail = false;
-  uint64_t spec_next = 0, spec_voff[2] = {0, 0};
-  for (int it = 0;; ++it) {
-    if (it >= kMaxChainIters) return fail(kErrState, "record chain did not converge");
-    after_stop_pending_ = false;  // (only the last iteration's stop counts)
-    // production runs check the inflate's DEFLATE status with the link
-    // check's read-back (one host round trip fewer; the chain kernels take
-    // any bytes, and their results are not used before the verdict)
-    const bool defer = !timing;
-    int rc = inflate(k0, inf_end, false, !defer);
-    bool check_pending = false;
-    if (rc == kOk && defer && inflate_queued_) {
-      HIPCHK(queue_inflate_check(k0, inf_end));
-      check_pending = true;
-    }
-    if (timing) {
-      infl_ms += times.inflate;
-      huff_ms += times.huff;
-      lz_ms += times.lz77;
-      tab_ms += times.tables;
-    }
-    if (rc != kOk) return rc;
-    a.u = du_.p;
-    a.e_inf = inf_end < nblk ? hblocks_[inf_end].ustart : total_u_;
-    a.k1 = k1;
-    const uint32_t nb = k1 - k0;
-    HIPCHK(g_.reserve(nb));
-    HIPCHK(x_.reserve(nb));
-    HIPCHK(x2_.reserve(nb));
-    HIPCHK(entry_.reserve(nb));
-    HIPCHK(summary_.reserve(4));
-    HIPCHK(cnt_.reserve(nb + 1));
-    HIPCHK(errv_.reserve(nb + 1));
-    HIPCHK(need_.reserve(1));
-    HIPCHK(rcand_.reserve(nb));
-    HIPCHK(force_.reserve(nb));
-    HIPCHK(wcnt_.reserve(nb));
-    HIPCHK(list_.reserve((uint64_t)nb * kListCap));
-    HIPCHK(base_arr_.reserve(nb + 1));
-    if (!counters_.p) {  // the cumulative words (kChainCtr..) are zeroed here only
-      HIPCHK(counters_.reserve(kChainCtrWords));
-      HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtrWords * 4, stream_));
-    }
-    size_t lsb = 0;
-    HIPCHK(link_scan_bytes(nb, &lsb));
-    HIPCHK(scan_tmp_.reserve(lsb + 16));
-    a.g = g_.p;
-    a.x = x_.p;
-    a.x2 = x2_.p;
-    a.entry = entry_.p;
-    a.summary = summary_.p;
-    a.cnt = cnt_.p;
-    a.err = errv_.p;
-    a.need = need_.p;
-    a.cand = rcand_.p;
-    a.force = force_.p;
-    a.wcnt = wcnt_.p;
-    a.list = list_.p;
-    a.counters = counters_.p;
-    a.base = base_arr_.p;
-    a.scan_tmp = scan_tmp_.p;
-    a.scan_bytes = lsb;
-    HIPCHK(hipMemsetAsync(need_.p, 0, 8, stream_));
-    HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtr * 4, stream_));  // the per-pass words only
-    HIPCHK(launch_chain(a, mode, kStageWalk, stream_));  // candidates + lane-per-block walks
-    // link: max-scan of the walk exits; re-walk blocks that are off the chain
-    bool serial = false;
-    // HBAM_CURSOR_TRACE: the blocks the link check left off the chain
-    auto dump_off_chain = [&]() {
-      if (!getenv("HBAM_CURSOR_TRACE")) return;
-      std::vector<uint64_t> fv(nb), gv(nb), xv(nb), ev(nb), inv(nb);
-      (void)hipStreamSynchronize(stream_);
-      (void)hipMemcpy(fv.data(), force_.p, nb * 8, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(gv.data(), g_.p, nb * 8, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(xv.data(), x_.p, nb * 8, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(ev.data(), entry_.p, nb * 8, hipMemcpyDeviceToHost);
-      (void)hipMemcpy(inv.data(), base_arr_.p, nb * 8, hipMemcpyDeviceToHost);
-      for (uint32_t i = 0, shown = 0; i < nb && shown < 8; ++i) {
-      if (fv[i] == ~0ull) continue;
-      const BlockInfo& b = hblocks_[a.k0 + i];
-      fprintf(stderr, "[chain]   block %u (of %u) ustart %llu end %llu: force %llx g %llx x %llx in %llx entry %llx\n",
-                i, nb, (unsigned long long)b.ustart, (unsigned long long)(b.ustart + b.isize),
-                (unsigned long long)fv[i], (unsigned long long)gv[i], (unsigned long long)xv[i],
-                (unsigned long long)inv[i], (unsigned long long)ev[i]);
-      ++shown;
-      }
-    };
-    uint64_t sm[2] = {0, 0};
-    unsigned long long need = 0;
-    // the lists' record counts scanned into base_arr_ (the output offsets of
-    // k_rec_check_out; their total bounds the span's records) and the list
-    // overflow flag come back with the chain's end in one host round trip
-    HIPCHK(fuse_.reserve(4));
-    uint64_t bound = 0, last_base = 0;
-    uint32_t ovf = 0, last_cnt = 0;
-    auto list_bound = [&]() -> hipError_t {
-      hipError_t e = launch_list_counts(a, stream_);
-      size_t tb = 0;
-      if (e == hipSuccess) e = scan_u32_to_u64(nullptr, &tb, cnt_.p, base_arr_.p, nb, stream_);
-      if (e == hipSuccess) e = scan_tmp_.reserve(tb + 16);
-      a.scan_tmp = scan_tmp_.p;  // (a grown buffer serves the next link check too)
-      if (e == hipSuccess) e = scan_u32_to_u64(scan_tmp_.p, &tb, cnt_.p, base_arr_.p, nb, stream_);
-      if (e == hipSuccess) e = rb(&last_base, base_arr_.p + nb - 1, 8, stream_);
-      if (e == hipSuccess) e = rb(&last_cnt, cnt_.p + nb - 1, 4, stream_);
-      if (e == hipSuccess) e = rb(&ovf, counters_.p + 2, 4, stream_);
-      return e;
-    };
-    // the chain's end: the link max-scan's last entry (read before
-    // list_bound's scan overwrites base_arr_) and the last block's exit
-    uint64_t t[2] = {0, 0};
-    auto chain_end = [&]() -> hipError_t {
-      hipError_t e = rb(&t[0], base_arr_.p + nb - 1, 8, stream_);
-      if (e == hipSuccess) e = rb(&t[1], x2_.p + nb - 1, 8, stream_);
-      return e;
-    };
-    bool spec_bound = false;  // chain end + list bound read with the first link check
-    bool early_zeroed = false;  // k_rec_check_out's counters zeroed with them
-    for (int fix = 0;; ++fix) {
-      HIPCHK(hipMemsetAsync(counters_.p, 0, 8, stream_));
-      HIPCHK(launch_chain(a, mode, kStageLinkCheck, stream_));
-      ++link_rounds_;
-      uint32_t ctr[2] = {0, 0};
-      HIPCHK(rb(ctr, counters_.p, 8, stream_));
-      // first round: queue the chain end and the list bound as if the link
-      // holds (it does in every production pass: link_rewalks 0); a re-walk
-      // or the serial link recomputes them
-      const bool spec = fix == 0 && !timing;
-      if (spec) {
-        HIPCHK(chain_end());
-        HIPCHK(list_bound());
-        // k_rec_check_out's counters too (they do not depend on the bound):
-        // after the host wait only its launch remains
-        HIPCHK(long_n_.reserve(1));
-        HIPCHK(hipMemsetAsync(long_n_.p, 0, 4, stream_));
-        HIPCHK(hipMemsetAsync(fuse_.p, 0xff, 12, stream_));  // early-stop key, first failing block: none
-        early_zeroed = true;
-      }
-      HIPCHK(rb_sync(stream_));
-      if (check_pending) {
-        check_pending = false;
-        if (int vr = inflate_verdict(k0, inf_end)) return vr;
-      }
-      if (spec && ctr[0] == 0 && ctr[1] == 0) {
-        spec_bound = true;
-        break;
-      }
-      if (ctr[0] || (ctr[1] && fix == kMaxLinkFix)) {
-        if (getenv("HBAM_CURSOR_TRACE"))
-          fprintf(stderr, "[chain] serial link: blocks [%u, %u) e_inf %llu e_true %llu p0 %llu rewalk round %d, "
-                  "%u blocks off the chain, serial request %u\n", a.k0, a.k1, (unsigned long long)a.e_inf,
-                  (unsigned long long)a.e_true, (unsigned long long)a.p0, fix, ctr[1], ctr[0]);
-        dump_off_chain();
-        serial = true;
-        break;
-      }
-      if (ctr[1] == 0) break;
-      if (getenv("HBAM_CURSOR_TRACE")) {
-        fprintf(stderr, "[chain] rewalk round %d: %u blocks off the chain\n", fix, ctr[1]);
-        dump_off_chain();
-      }
-      ++link_rewalks_;
-      HIPCHK(launch_chain(a, mode, kStageRewalk, stream_));
-    }
-    if (serial) {  // exact serial link (writes entry[] + summary), then lists off entry[]
-      ++link_fallbacks_;
-      HIPCHK(launch_chain(a, mode, kStageSerialLink, stream_));
-      HIPCHK(launch_chain(a, mode, kStageRewalkAll, stream_));
-      HIPCHK(rb(sm, summary_.p, 16, stream_));
-      HIPCHK(list_bound());
-      HIPCHK(rb_sync(stream_));
-    } else {  // final chain position = max of every walk exit; no stop
-      if (!spec_bound) {
-        HIPCHK(chain_end());
-        HIPCHK(list_bound());
-        HIPCHK(rb_sync(stream_));
-      }
-      sm[0] = nb == 1 ? t[1] : std::max(t[0], t[1]);
-      sm[1] = 0;
-    }
-    bound = last_base + last_cnt;
-    lists = ovf == 0;
-    // a list overflowed (indexer mode: records shorter than 36 bytes): the
-    // per-block walks count and emit the records instead (k_rec_count,
-    // k_rec_emit)
-    fused = lists;
-    if (!lists) ++record_fallbacks_;
-    if (fused) {
-      // outputs sized by the lists' records, then check + positions + voffs +
-      // fields + keys in one launch, each block at its scanned list offset
-      HIPCHK(rec_pos_.reserve(bound + 1));
-      HIPCHK(rec_voff_.reserve(bound + 1));
-      if (dec) {
-        int rc = alloc_columns(bound, total_u_, &c, !early_zeroed);
-        if (rc != kOk) return rc;
-      }
-      if (!early_zeroed) HIPCHK(hipMemsetAsync(fuse_.p, 0xff, 12, stream_));  // early-stop key, first failing block: none
-      a.fuse_bad = reinterpret_cast<uint64_t*>(fuse_.p);
-      a.fuse_flags = fuse_.p + 2;
-      a.rec_pos = rec_pos_.p;
-      a.rec_voff = rec_voff_.p;
-      if (timing) HIPCHK(hipEventRecord(ev_[1], stream_));
-      HIPCHK(launch_rec_check_out(a, mode, dec, c, bound + 1, stream_));
-      const bool spec = !timing;
-      if (spec) {
-        const unsigned long long* gb = reinterpret_cast<const unsigned long long*>(fuse_.p);
-        if (dec) HIPCHK(launch_long_hash(du_.p, rec_pos_.p, c, stream_, gb, need_.p, a.e_inf));
-        HIPCHK(scalars_.reserve(8));
-        HIPCHK(launch_next_pos(du_.p, rec_pos_.p, bound, p0, mode, scalars_.p, stream_, gb, need_.p, a.e_inf));
-        HIPCHK(rb(&spec_next, scalars_.p, 8, stream_));
-        if (bound) {  // (stale unless the gate opens: then unused)
-          HIPCHK(rb(&spec_voff[0], rec_voff_.p, 8, stream_));
-          HIPCHK(rb(&spec_voff[1], rec_voff_.p + bound - 1, 8, stream_));
-        }
-      }
-      uint64_t bad = 0;
-      uint32_t fl[2] = {0, 0};
-      HIPCHK(rb(&need, need_.p, 8, stream_));
-      HIPCHK(rb(&bad, fuse_.p, 8, stream_));
-      HIPCHK(rb(fl, fuse_.p + 2, 4, stream_));
-      HIPCHK(rb_sync(stream_));
-      spec_tail = spec && bad == ~0ull && need <= a.e_inf;
-      fused_first = fl[0];
-      if (bad == ~0ull) {
-        fused_total = bound;  // every block kept its whole list
-      } else {
-        // the span ends at the first block that stops: its records stand at
-        // their final offsets, later blocks' records lie past them and are
-        // dropped, and that block's status (if any) is the span's -- a
-        // failure in a later block is never reached (k_rec_check_out)
-        const uint64_t k = bad >> kFusedBadShift;
-        fused_total = bad & ((1ull << kFusedBadShift) - 1);
-        if (fl[0] != k) fused_first = 0xffffffffu;
-        // (diagnostic) records listed after the stop, which it drops: read
-        // with the span's last readback, no round trip of its own
-        HIPCHK(hipMemsetAsync(fuse_.p + 3, 0, 4, stream_));
-        HIPCHK(launch_records_after(cnt_.p, nb, (uint32_t)k, fuse_.p + 3, stream_));
-        HIPCHK(rb(&after_stop_flag_, fuse_.p + 3, 4, stream_));
-        after_stop_pending_ = true;
-      }
-    } else {
-      HIPCHK(launch_chain(a, mode, kStageCount, stream_));  // count + validate by walking
-      HIPCHK(rb(&need, need_.p, 8, stream_));
-      HIPCHK(rb_sync(stream_));
-    }
-    const uint64_t final_pos = sm[0];
-    const bool stopped = sm[1] != 0;
-    if (need > a.e_inf && inf_end < nblk) {  // a record needs bytes beyond the inflated range
-      inf_end = std::min(nblk, block_containing(std::min<uint64_t>(need, total_u_) - 1) + 2);
-      continue;
-    }
-    if (stopped && final_pos + 36 > a.e_inf && inf_end < nblk) {
-      inf_end = std::min(nblk, inf_end + 4);
-      continue;
-    }
-    if (!stopped && final_pos < q_end && final_pos < total_u_ && k1 < nblk && final_pos >= hblocks_[k1].ustart) {
-      k1 = std::min(nblk, block_containing(std::min(final_pos, q_end - 1)) + 1);
-      inf_end = std::max(inf_end, std::min(nblk, k1 + 2));
-      continue;
-    }
-    break;
+  return true;
+}
+
+// Reads k0, inf_end, ahead.  Queues the inflate of the blocks of [k0,
+// inf_end) not inflated yet.  A timed pass checks the DEFLATE status at once
+// (the host wait is inside inflate()) and adds the stage times to s.  A
+// production pass queues the check's read-back and sets s.check_pending:
+// the verdict lands with span_link's first read-back (one host round trip
+// fewer; the chain kernels take any bytes, and their results are not used
+// before the verdict).  No host wait of its own.
+int Pipeline::span_inflate(SpanPass& s) {
+  const int rc = inflate(s.k0, s.inf_end, false, !s.ahead);
+  s.check_pending = false;
+  if (rc == kOk && s.ahead && inflate_queued_) {
+    HIPCHK(queue_inflate_check(s.k0, s.inf_end));
+    s.check_pending = true;
   }
-  const uint32_t nb = k1 - k0;
-  // first failing block: records before it stand, later blocks are dropped
-  const uint32_t none = 0xffffffffu;
-  uint32_t first = fused_first;
-  if (!fused) {
-    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 3), (int)none, 1, stream_));
-    HIPCHK(launch_first_error_i32(errv_.p, nb, flags_.p + 3, stream_));
-    HIPCHK(rb(&first, flags_.p + 3, 4, stream_));
-    HIPCHK(rb_sync(stream_));
-  }
-  int32_t code = 0;
-  if (first != none) {
-    HIPCHK(rb(&code, errv_.p + first, 4, stream_));
-    HIPCHK(rb_sync(stream_));
-    // (k_rec_count) the first block that stops, with or without an error:
-    // the iteration ends there
-    if (!fused) HIPCHK(launch_truncate_counts(cnt_.p, nb, flags_.p + 3, stream_));
-  }
-  if (first != none && code != kStopClean) {
-    out->status = code;
-    const BlockInfo& b = hblocks_[k0 + first];
-    const char* what = code == kErrFormat ? "Invalid record (SAMFormatException)"
-                       : code == kErrTrunc ? "Premature EOF in BAM record"
-                       : code == kErrArg   ? "Reference index not found in sequence dictionary"
-                                           : "Invalid alignment";
-    out->error = std::string(what) + " (BGZF block at offset " + std::to_string(b.coff) + ")";
-  }
-  uint64_t total = fused_total;
-  if (!fused) {
-    HIPCHK(base_arr_.reserve(nb + 1));
-    size_t tb = 0;
-    HIPCHK(scan_u32_to_u64(nullptr, &tb, cnt_.p, base_arr_.p, nb, stream_));
-    HIPCHK(scan_tmp_.reserve(tb + 16));
-    HIPCHK(scan_u32_to_u64(scan_tmp_.p, &tb, cnt_.p, base_arr_.p, nb, stream_));
-    uint64_t last_base = 0;
-    uint32_t last_cnt = 0;
-    HIPCHK(rb(&last_base, base_arr_.p + nb - 1, 8, stream_));
-    HIPCHK(rb(&last_cnt, cnt_.p + nb - 1, 4, stream_));
-    HIPCHK(rb_sync(stream_));
-    total = last_base + last_cnt;
-    HIPCHK(rec_pos_.reserve(total + 1));
-    HIPCHK(rec_voff_.reserve(total + 1));
-    a.base = base_arr_.p;
-    a.rec_pos = rec_pos_.p;
-    a.rec_voff = rec_voff_.p;
-    if (dec) {
-      int rc = alloc_columns(total, total_u_, &c);
-      if (rc != kOk) return rc;
-    }
-  }
-  out->n = total;
-  out->rec_pos = rec_pos_.p;
-  out->rec_voff = rec_voff_.p;
-  if (dec) out->col = c;
-  if (!fused) {  // a block listed more starts than kListCap: per-block walks
-    HIPCHK(launch_chain(a, mode, kStageEmit, stream_));
-    if (timing) HIPCHK(hipEventRecord(ev_[1], stream_));
-    if (dec) HIPCHK(launch_rec_decode(du_.p, rec_pos_.p, total, c, stream_));
-  }
-  if (fused && spec_tail) {  // (then total == bound: no block stopped the span)
-    out->next_pos = spec_next;  // (done and read with k_rec_check_out's verdict)
-    out->first_voff = spec_voff[0];
-    out->last_voff = spec_voff[1];
-  } else {
-    if (total) {
-      HIPCHK(rb(&out->first_voff, rec_voff_.p, 8, stream_));
-      HIPCHK(rb(&out->last_voff, rec_voff_.p + total - 1, 8, stream_));
-    }
-    if (dec) HIPCHK(launch_long_hash(du_.p, rec_pos_.p, c, stream_));
-    // the next record's start: the chain successor of the last record
-    HIPCHK(scalars_.reserve(8));
-    HIPCHK(launch_next_pos(du_.p, rec_pos_.p, total, p0, mode, scalars_.p, stream_));
-    HIPCHK(rb(&out->next_pos, scalars_.p, 8, stream_));
-    if (timing) HIPCHK(hipEventRecord(ev_[2], stream_));
-    HIPCHK(rb_sync(stream_));
-  }
-  if (after_stop_pending_ && after_stop_flag_) ++records_after_stop_;
-  after_stop_pending_ = false;
-  after_stop_flag_ = 0;
   if (timing) {
-    float all = 0, dcd = 0;
-    (void)hipEventElapsedTime(&all, ev_[0], ev_[1]);
-    (void)hipEventElapsedTime(&dcd, ev_[1], ev_[2]);
-    times.chain = all - infl_ms;
-    times.decode = dcd;
-    times.inflate = infl_ms;
-    times.huff = huff_ms;
-    times.lz77 = lz_ms;
-    times.tables = tab_ms;
+    s.infl_ms += times.inflate;
+    s.huff_ms += times.huff;
+    s.lz_ms += times.lz77;
+    s.tab_ms += times.tables;
+  }
+  return rc;
+}
+
+// Reads k0, k1, inf_end.  Sizes the per-block scratch for nb = k1 - k0
+// blocks and leaves its pointers, u, e_inf and k1 in s.a.  Queues: the zero
+// of counters_' cumulative words (on its first allocation only), of need_ and
+// of the per-pass counter words, then the walks (candidates + lane-per-block
+// walks).  No host wait (a buffer that grows waits for the streams).
+int Pipeline::span_scratch(SpanPass& s) {
+  ChainArgs& a = s.a;
+  a.u = du_.p;
+  a.e_inf = s.inf_end < s.nblk ? hblocks_[s.inf_end].ustart : total_u_;
+  a.k1 = s.k1;
+  const uint32_t nb = s.k1 - s.k0;
+  HIPCHK(g_.reserve(nb));
+  HIPCHK(x_.reserve(nb));
+  HIPCHK(x2_.reserve(nb));
+  HIPCHK(entry_.reserve(nb));
+  HIPCHK(summary_.reserve(4));
+  HIPCHK(cnt_.reserve(nb + 1));
+  HIPCHK(errv_.reserve(nb + 1));
+  HIPCHK(need_.reserve(1));
+  HIPCHK(rcand_.reserve(nb));
+  HIPCHK(force_.reserve(nb));
+  HIPCHK(wcnt_.reserve(nb));
+  HIPCHK(list_.reserve((uint64_t)nb * kListCap));
+  HIPCHK(base_arr_.reserve(nb + 1));
+  if (!counters_.p) {  // the cumulative words (kChainCtr..) are zeroed here only
+    HIPCHK(counters_.reserve(kChainCtrWords));
+    HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtrWords * 4, stream_));
+  }
+  size_t lsb = 0;
+  HIPCHK(link_scan_bytes(nb, &lsb));
+  HIPCHK(scan_tmp_.reserve(lsb + 16));
+  HIPCHK(fuse_.reserve(4));
+  a.g = g_.p;
+  a.x = x_.p;
+  a.x2 = x2_.p;
+  a.entry = entry_.p;
+  a.summary = summary_.p;
+  a.cnt = cnt_.p;
+  a.err = errv_.p;
+  a.need = need_.p;
+  a.cand = rcand_.p;
+  a.force = force_.p;
+  a.wcnt = wcnt_.p;
+  a.list = list_.p;
+  a.counters = counters_.p;
+  a.base = base_arr_.p;
+  a.scan_tmp = scan_tmp_.p;
+  a.scan_bytes = lsb;
+  HIPCHK(hipMemsetAsync(need_.p, 0, 8, stream_));
+  HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtr * 4, stream_));  // the per-pass words only
+  HIPCHK(launch_chain(a, s.mode, kStageWalk, stream_));  // candidates + lane-per-block walks
+  return kOk;
+}
+
+// HBAM_CURSOR_TRACE: the blocks the link check left off the chain (waits for
+// the stream).  base_arr_ holds the link's max-scan ("in") unless list_bound
+// was queued behind this check round: then its scan has put the list offsets there.
+void Pipeline::dump_off_chain(const SpanPass& s, bool list_offsets_in_base) {
+  const uint32_t nb = s.a.k1 - s.a.k0;
+  std::vector<uint64_t> fv(nb), gv(nb), xv(nb), ev(nb), inv(nb);
+  (void)hipStreamSynchronize(stream_);
+  (void)hipMemcpy(fv.data(), force_.p, nb * 8, hipMemcpyDeviceToHost);
+  (void)hipMemcpy(gv.data(), g_.p, nb * 8, hipMemcpyDeviceToHost);
+  (void)hipMemcpy(xv.data(), x_.p, nb * 8, hipMemcpyDeviceToHost);
+  (void)hipMemcpy(ev.data(), entry_.p, nb * 8, hipMemcpyDeviceToHost);
+  (void)hipMemcpy(inv.data(), base_arr_.p, nb * 8, hipMemcpyDeviceToHost);
+  for (uint32_t i = 0, shown = 0; i < nb && shown < 8; ++i) {
+    if (fv[i] == ~0ull) continue;
+    const BlockInfo& b = hblocks_[s.a.k0 + i];
+    fprintf(stderr, "[chain]   block %u (of %u) ustart %llu end %llu: force %llx g %llx x %llx %s %llx entry %llx\n",
+            i, nb, (unsigned long long)b.ustart, (unsigned long long)(b.ustart + b.isize),
+            (unsigned long long)fv[i], (unsigned long long)gv[i], (unsigned long long)xv[i],
+            list_offsets_in_base ? "list offset" : "in", (unsigned long long)inv[i], (unsigned long long)ev[i]);
+    ++shown;
+  }
+}
+
+// The chain's end, queued as read-backs into s.end: the link max-scan's last
+// entry (it must be read before list_offsets' scan overwrites base_arr_) and
+// the last block's exit.
+hipError_t Pipeline::chain_end(SpanPass& s) {
+  const uint32_t nb = s.a.k1 - s.a.k0;
+  hipError_t e = rb(&s.end[0], base_arr_.p + nb - 1, 8, stream_);
+  if (e == hipSuccess) e = rb(&s.end[1], x2_.p + nb - 1, 8, stream_);
+  return e;
+}
+
+// cnt_ scanned into base_arr_ (a block's output offset); the last offset and
+// count, whose sum is the total, queued as read-backs into s.last_base /
+// s.last_cnt.  The scan may grow scan_tmp_: s.a.scan_tmp follows it (the
+// grown buffer serves the next link check too).
+hipError_t Pipeline::list_offsets(SpanPass& s) {
+  const uint32_t nb = s.a.k1 - s.a.k0;
+  size_t tb = 0;
+  hipError_t e = scan_u32_to_u64(nullptr, &tb, cnt_.p, base_arr_.p, nb, stream_);
+  if (e == hipSuccess) e = scan_tmp_.reserve(tb + 16);
+  s.a.scan_tmp = scan_tmp_.p;
+  if (e == hipSuccess) e = scan_u32_to_u64(scan_tmp_.p, &tb, cnt_.p, base_arr_.p, nb, stream_);
+  if (e == hipSuccess) e = rb(&s.last_base, base_arr_.p + nb - 1, 8, stream_);
+  if (e == hipSuccess) e = rb(&s.last_cnt, cnt_.p + nb - 1, 4, stream_);
+  return e;
+}
+
+// The lists' record counts (k_list_counts -> cnt_) scanned into base_arr_
+// (the output offsets of k_rec_check_out; their total bounds the span's
+// records) and the list overflow flag, queued as read-backs into s.last_base,
+// s.last_cnt, s.ovf: they come back with the chain's end in one host round trip.
+hipError_t Pipeline::list_bound(SpanPass& s) {
+  hipError_t e = launch_list_counts(s.a, stream_);
+  if (e == hipSuccess) e = list_offsets(s);
+  if (e == hipSuccess) e = rb(&s.ovf, counters_.p + 2, 4, stream_);
+  return e;
+}
+
+// The link: a max-scan of the walk exits that asks blocks off the chain to be
+// re-walked, in rounds; after kMaxLinkFix rounds, or on a hard violation, the
+// exact serial link.  Reads s.a, ahead, check_pending.  Queues per round the
+// zero of the round's two counter words, the link check and its read-back
+// (s.ctr), then a host wait.  A production pass queues behind the first round,
+// as if the link holds (it does in every production pass: link_rewalks 0),
+// chain_end, list_bound and the zero of k_rec_check_out's long_n_ and fuse_
+// words (after the host wait only its launch remains; span_check_out skips
+// them when s.ahead); a re-walk or the serial link computes end and bound
+// again, with one more host wait, as does a timed pass.  The inflate's
+// verdict (check_pending) is taken after the first wait.  Leaves in s: sm
+// (final position, stopped), bound, ovf, lists.
+int Pipeline::span_link(SpanPass& s) {
+  const uint32_t nb = s.a.k1 - s.a.k0;
+  bool serial = false, held = false;
+  for (int fix = 0;; ++fix) {
+    HIPCHK(hipMemsetAsync(counters_.p, 0, 8, stream_));
+    HIPCHK(launch_chain(s.a, s.mode, kStageLinkCheck, stream_));
+    ++link_rounds_;
+    HIPCHK(rb(s.ctr, counters_.p, 8, stream_));
+    const bool spec = fix == 0 && s.ahead;
+    if (spec) {
+      HIPCHK(chain_end(s));
+      HIPCHK(list_bound(s));
+      HIPCHK(long_n_.reserve(1));
+      HIPCHK(hipMemsetAsync(long_n_.p, 0, 4, stream_));
+      HIPCHK(hipMemsetAsync(fuse_.p, 0xff, 12, stream_));  // early-stop key, first failing block: none
+    }
+    HIPCHK(rb_sync(stream_));
+    if (s.check_pending) {
+      s.check_pending = false;
+      if (int vr = inflate_verdict(s.k0, s.inf_end)) return vr;
+    }
+    const bool linked = s.ctr[0] == 0 && s.ctr[1] == 0;
+    held = spec && linked;  // what was queued behind this round stands
+    if (linked) break;
+    serial = s.ctr[0] || fix == kMaxLinkFix;
+    if (cursor_trace()) {
+      if (serial)
+        fprintf(stderr, "[chain] serial link: blocks [%u, %u) e_inf %llu e_true %llu p0 %llu rewalk round %d, "
+                "%u blocks off the chain, serial request %u\n", s.a.k0, s.a.k1, (unsigned long long)s.a.e_inf,
+                (unsigned long long)s.a.e_true, (unsigned long long)s.a.p0, fix, s.ctr[1], s.ctr[0]);
+      else
+        fprintf(stderr, "[chain] rewalk round %d: %u blocks off the chain\n", fix, s.ctr[1]);
+      dump_off_chain(s, spec);
+    }
+    if (serial) break;
+    ++link_rewalks_;
+    HIPCHK(launch_chain(s.a, s.mode, kStageRewalk, stream_));
+  }
+  if (serial) {  // exact serial link (writes entry[] + summary), then lists off entry[]
+    ++link_fallbacks_;
+    HIPCHK(launch_chain(s.a, s.mode, kStageSerialLink, stream_));
+    HIPCHK(launch_chain(s.a, s.mode, kStageRewalkAll, stream_));
+    HIPCHK(rb(s.sm, summary_.p, 16, stream_));
+    HIPCHK(list_bound(s));
+    HIPCHK(rb_sync(stream_));
+  } else {  // final chain position = max of every walk exit; no stop
+    if (!held) {
+      HIPCHK(chain_end(s));
+      HIPCHK(list_bound(s));
+      HIPCHK(rb_sync(stream_));
+    }
+    s.sm[0] = nb == 1 ? s.end[1] : std::max(s.end[0], s.end[1]);
+    s.sm[1] = 0;
+  }
+  s.bound = s.last_base + s.last_cnt;
+  // a list overflowed (indexer mode: records shorter than 36 bytes): the
+  // per-block walks count and emit the records instead (k_rec_count, k_rec_emit)
+  s.lists = s.ovf == 0;
+  if (!s.lists) ++record_fallbacks_;
+  return kOk;
+}
+
+// The list path.  Reads s.a, bound, dec, ahead.  Sizes the outputs by the
+// lists' records, then queues check + positions + voffs + fields + keys in
+// one launch (k_rec_check_out), each block at its scanned list offset; a
+// production pass queues the span's tail behind it, gated on its verdict
+// (span_tail), and skips the zero of long_n_ and fuse_ that span_link queued.
+// One host wait reads need, bad, fl (and the tail).  Leaves total, first,
+// tail_done; when a block stopped the span, the records-after-stop flag is
+// queued too and lands with the span's last read-back.
+int Pipeline::span_check_out(SpanPass& s) {
+  ChainArgs& a = s.a;
+  HIPCHK(rec_pos_.reserve(s.bound + 1));
+  HIPCHK(rec_voff_.reserve(s.bound + 1));
+  if (s.dec) {
+    const int rc = alloc_columns(s.bound, total_u_, &s.c, !s.ahead);
+    if (rc != kOk) return rc;
+  }
+  if (!s.ahead) HIPCHK(hipMemsetAsync(fuse_.p, 0xff, 12, stream_));  // early-stop key, first failing block: none
+  a.fuse_bad = reinterpret_cast<uint64_t*>(fuse_.p);
+  a.fuse_flags = fuse_.p + 2;
+  a.rec_pos = rec_pos_.p;
+  a.rec_voff = rec_voff_.p;
+  if (timing) HIPCHK(hipEventRecord(ev_[1], stream_));
+  HIPCHK(launch_rec_check_out(a, s.mode, s.dec, s.c, s.bound + 1, stream_));
+  if (s.ahead)
+    if (int rc = span_tail(s, s.bound, true)) return rc;
+  HIPCHK(rb(&s.need, need_.p, 8, stream_));
+  HIPCHK(rb(&s.bad, fuse_.p, 8, stream_));
+  HIPCHK(rb(s.fl, fuse_.p + 2, 4, stream_));
+  HIPCHK(rb_sync(stream_));
+  s.tail_done = s.ahead && s.bad == ~0ull && s.need <= a.e_inf;
+  s.first = s.fl[0];
+  s.total = s.bound;  // every block kept its whole list
+  if (s.bad != ~0ull) {
+    // the span ends at the first block that stops: its records stand at
+    // their final offsets, later blocks' records lie past them and are
+    // dropped, and that block's status (if any) is the span's -- a
+    // failure in a later block is never reached (k_rec_check_out)
+    const uint64_t k = s.bad >> kFusedBadShift;
+    s.total = s.bad & ((1ull << kFusedBadShift) - 1);
+    if (s.fl[0] != k) s.first = kNoBlock;
+    // (diagnostic) records listed after the stop, which it drops: read
+    // with the span's last readback, no round trip of its own
+    HIPCHK(hipMemsetAsync(fuse_.p + 3, 0, 4, stream_));
+    HIPCHK(launch_records_after(cnt_.p, a.k1 - a.k0, (uint32_t)k, fuse_.p + 3, stream_));
+    HIPCHK(rb(&after_stop_flag_, fuse_.p + 3, 4, stream_));
+    after_stop_pending_ = true;
   }
   return kOk;
+}
+
+// The walk path (a list overflowed).  Queues the count + validation by
+// walking (k_rec_count) and the read-back of need; one host wait.
+int Pipeline::span_count(SpanPass& s) {
+  s.tail_done = false;
+  HIPCHK(launch_chain(s.a, s.mode, kStageCount, stream_));
+  HIPCHK(rb(&s.need, need_.p, 8, stream_));
+  HIPCHK(rb_sync(stream_));
+  return kOk;
+}
+
+// Go round again?  Reads need, sm, s.a.e_inf / q_end and the block table;
+// changes only k1 and inf_end.  Queues nothing.
+bool Pipeline::span_grow(SpanPass& s) {
+  const uint64_t final_pos = s.sm[0], e_inf = s.a.e_inf, q_end = s.a.q_end;
+  const bool stopped = s.sm[1] != 0;
+  const uint32_t nblk = s.nblk;
+  if (s.need > e_inf && s.inf_end < nblk) {  // a record needs bytes beyond the inflated range
+    s.inf_end = std::min(nblk, block_containing(std::min<uint64_t>(s.need, total_u_) - 1) + 2);
+    return true;
+  }
+  if (stopped && final_pos + 36 > e_inf && s.inf_end < nblk) {  // the chain stopped for want of bytes
+    s.inf_end = std::min(nblk, s.inf_end + 4);
+    return true;
+  }
+  if (!stopped && final_pos < q_end && final_pos < total_u_ && s.k1 < nblk && final_pos >= hblocks_[s.k1].ustart) {
+    // the chain runs on inside the span past block k1 - 1: take the blocks up to its end
+    s.k1 = std::min(nblk, block_containing(std::min(final_pos, q_end - 1)) + 1);
+    s.inf_end = std::max(s.inf_end, std::min(nblk, s.k1 + 2));
+    return true;
+  }
+  return false;
+}
+
+// The first failing block (s.first; none: nothing to do): records before it
+// stand, later blocks are dropped.  Queues the read-back of its status
+// (s.code); one host wait.  Unless the block stopped cleanly, leaves the
+// status and its text in *out.
+int Pipeline::span_status(SpanPass& s, SpanDev* out) {
+  if (s.first == kNoBlock) return kOk;
+  HIPCHK(rb(&s.code, errv_.p + s.first, 4, stream_));
+  HIPCHK(rb_sync(stream_));
+  if (s.code == kStopClean) return kOk;
+  out->status = s.code;
+  const BlockInfo& b = hblocks_[s.k0 + s.first];
+  const char* what = s.code == kErrFormat ? "Invalid record (SAMFormatException)"
+                     : s.code == kErrTrunc ? "Premature EOF in BAM record"
+                     : s.code == kErrArg   ? "Reference index not found in sequence dictionary"
+                                           : "Invalid alignment";
+  out->error = std::string(what) + " (BGZF block at offset " + std::to_string(b.coff) + ")";
+  return kOk;
+}
+
+// The walk path's output (a block listed more starts than kListCap), after
+// the last span_count.  Queues the first failing block's search and read-back
+// (a host wait), span_status (one more if there is one), the cut of the
+// counts at that block -- the first block that stops, with or without an
+// error: the iteration ends there --, list_offsets (a host wait: s.total),
+// then the per-block walks that emit positions + voffs (k_rec_emit) and
+// k_rec_decode.  Leaves first, code, total, c and the outputs' pointers in s.a.
+int Pipeline::span_emit_walks(SpanPass& s, SpanDev* out) {
+  ChainArgs& a = s.a;
+  const uint32_t nb = a.k1 - a.k0;
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 3), (int)kNoBlock, 1, stream_));
+  HIPCHK(launch_first_error_i32(errv_.p, nb, flags_.p + 3, stream_));
+  HIPCHK(rb(&s.first, flags_.p + 3, 4, stream_));
+  HIPCHK(rb_sync(stream_));
+  if (int rc = span_status(s, out)) return rc;
+  if (s.first != kNoBlock) HIPCHK(launch_truncate_counts(cnt_.p, nb, flags_.p + 3, stream_));
+  HIPCHK(list_offsets(s));
+  HIPCHK(rb_sync(stream_));
+  s.total = s.last_base + s.last_cnt;
+  HIPCHK(rec_pos_.reserve(s.total + 1));
+  HIPCHK(rec_voff_.reserve(s.total + 1));
+  a.rec_pos = rec_pos_.p;
+  a.rec_voff = rec_voff_.p;
+  if (s.dec) {
+    const int rc = alloc_columns(s.total, total_u_, &s.c);
+    if (rc != kOk) return rc;
+  }
+  HIPCHK(launch_chain(a, s.mode, kStageEmit, stream_));
+  if (timing) HIPCHK(hipEventRecord(ev_[1], stream_));
+  if (s.dec) HIPCHK(launch_rec_decode(du_.p, rec_pos_.p, s.total, s.c, stream_));
+  return kOk;
+}
+
+// The span's tail over its n records.  Queues the deferred long keys
+// (k_long_hash, when dec), the next record's start -- the chain successor of
+// the last record (k_next_pos) -- and the read-backs of it and of the first
+// and last voff into s.next, s.voff.  gated: queued behind k_rec_check_out
+// before its verdict is known; the two kernels do nothing unless it found no
+// stop and no record needs bytes past e_inf, and the words read are stale
+// then (unused: tail_done stays false).  No host wait: the caller's follows.
+int Pipeline::span_tail(SpanPass& s, uint64_t n, bool gated) {
+  const unsigned long long* gate_bad = gated ? reinterpret_cast<const unsigned long long*>(fuse_.p) : nullptr;
+  const unsigned long long* gate_need = gated ? need_.p : nullptr;
+  const uint64_t gate_e_inf = gated ? s.a.e_inf : 0;
+  s.voff[0] = s.voff[1] = 0;
+  if (s.dec) HIPCHK(launch_long_hash(du_.p, rec_pos_.p, s.c, stream_, gate_bad, gate_need, gate_e_inf));
+  HIPCHK(scalars_.reserve(8));
+  HIPCHK(launch_next_pos(du_.p, rec_pos_.p, n, s.a.p0, s.mode, scalars_.p, stream_, gate_bad, gate_need, gate_e_inf));
+  HIPCHK(rb(&s.next, scalars_.p, 8, stream_));
+  if (n) {
+    HIPCHK(rb(&s.voff[0], rec_voff_.p, 8, stream_));
+    HIPCHK(rb(&s.voff[1], rec_voff_.p + n - 1, 8, stream_));
+  }
+  return kOk;
+}
+
+// A timed pass's stage times, from the events the steps recorded (ev_[0]
+// the pass's start, [1] before the check-out or decode, [2] its end) and the
+// inflates' sums in s.
+void Pipeline::span_times(const SpanPass& s) {
+  float all = 0, dcd = 0;
+  (void)hipEventElapsedTime(&all, ev_[0], ev_[1]);
+  (void)hipEventElapsedTime(&dcd, ev_[1], ev_[2]);
+  times.chain = all - s.infl_ms;
+  times.decode = dcd;
+  times.inflate = s.infl_ms;
+  times.huff = s.huff_ms;
+  times.lz77 = s.lz_ms;
+  times.tables = s.tab_ms;
 }
 
 int Pipeline::alloc_columns(uint64_t total, uint64_t stream_bytes, Columns* cp, bool zero_long_n) {
@@ -1326,27 +1410,22 @@ int Pipeline::alloc_columns(uint64_t total, uint64_t stream_bytes, Columns* cp, 
   }
   HIPCHK(rec_voff_.reserve(n + 1));
   uint8_t* p = cols_.p;
-  auto take = [&](uint64_t bytes) {
-    uint8_t* r = p;
-    p += (bytes + 15) & ~15ull;
-    return r;
-  };
   Columns& c = *cp;
-  c.key = reinterpret_cast<int64_t*>(take(8 * n));
-  c.rest_off = reinterpret_cast<uint64_t*>(take(8 * n));
+  c.key = reinterpret_cast<int64_t*>(take16(&p, 8 * n));
+  c.rest_off = reinterpret_cast<uint64_t*>(take16(&p, 8 * n));
   c.voff = rec_voff_.p;
-  c.ref_id = reinterpret_cast<int32_t*>(take(4 * n));
-  c.pos = reinterpret_cast<int32_t*>(take(4 * n));
-  c.l_seq = reinterpret_cast<int32_t*>(take(4 * n));
-  c.next_ref_id = reinterpret_cast<int32_t*>(take(4 * n));
-  c.next_pos = reinterpret_cast<int32_t*>(take(4 * n));
-  c.tlen = reinterpret_cast<int32_t*>(take(4 * n));
-  c.rest_len = reinterpret_cast<uint32_t*>(take(4 * n));
-  c.bin = reinterpret_cast<uint16_t*>(take(2 * n));
-  c.n_cigar = reinterpret_cast<uint16_t*>(take(2 * n));
-  c.flag = reinterpret_cast<uint16_t*>(take(2 * n));
-  c.l_read_name = take(n);
-  c.mapq = take(n);
+  c.ref_id = reinterpret_cast<int32_t*>(take16(&p, 4 * n));
+  c.pos = reinterpret_cast<int32_t*>(take16(&p, 4 * n));
+  c.l_seq = reinterpret_cast<int32_t*>(take16(&p, 4 * n));
+  c.next_ref_id = reinterpret_cast<int32_t*>(take16(&p, 4 * n));
+  c.next_pos = reinterpret_cast<int32_t*>(take16(&p, 4 * n));
+  c.tlen = reinterpret_cast<int32_t*>(take16(&p, 4 * n));
+  c.rest_len = reinterpret_cast<uint32_t*>(take16(&p, 4 * n));
+  c.bin = reinterpret_cast<uint16_t*>(take16(&p, 2 * n));
+  c.n_cigar = reinterpret_cast<uint16_t*>(take16(&p, 2 * n));
+  c.flag = reinterpret_cast<uint16_t*>(take16(&p, 2 * n));
+  c.l_read_name = take16(&p, n);
+  c.mapq = take16(&p, n);
   // deferred long-record keys: at most one per kLongHash stream bytes
   const uint64_t cap = std::min<uint64_t>(stream_bytes / kLongHash + 64, 0xffffffffull);
   HIPCHK(long_rec_.reserve(cap));

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "hbam_device.h"
+#include "hbam_launch.h"  // ChainArgs (SpanPass)
 
 namespace hbam {
 
@@ -206,6 +207,11 @@ class Pipeline {
   // synchronizes s in any case.
   hipError_t rb(void* dst, const void* src, size_t bytes, hipStream_t s);
   hipError_t rb_sync(hipStream_t s);
+  // Forget the queued reads without copying: the queue holds raw host
+  // addresses, mostly of the caller's frame, and a call that fails returns
+  // before its rb_sync.  hip_check does this on every failure; a caller with
+  // an error path of its own does it there.
+  void rb_cancel();
   // dst (device) <- file bytes [off, off + len) of src through the copy
   // threads and bounce buffers (HostFeed), synchronously on the pipeline's
   // stream (a short read of src: kErrTrunc)
@@ -273,7 +279,28 @@ class Pipeline {
   // inside the window (out->next_pos = its start).
   int decode_span(uint64_t vstart, uint64_t vend, ChainMode mode, bool decode, SpanDev* out);
   // Same, from a window position (index mode: a carried position may lie
-  // past the first block).
+  // past the first block).  The pass is a sequence of steps over one SpanPass
+  // (private, below), in this order:
+  //   span_range      blocks [k0, k1) of the span, the inflate's end, the constant ChainArgs
+  //   per round, until span_grow has nothing to add:
+  //     span_inflate    blocks [k0, inf_end); the DEFLATE verdict rides with the link's read-back
+  //     span_scratch    buffers, ChainArgs pointers, per-pass memsets, the walks
+  //     span_link       link check (+ re-walk rounds or the serial link); chain end, list bound
+  //     span_check_out  lists hold every record: check + output in one launch, the tail behind it
+  //     span_count      a list overflowed: count + validate by walking
+  //     span_grow       inflate further / take more blocks and go round again?
+  //   span_status     the first failing block's status and text
+  //   span_emit_walks (a list overflowed) offsets, outputs, k_rec_emit, k_rec_decode
+  //   span_tail       long keys, the next record's start, first / last voff
+  //                   (unless span_check_out's ran and its gate opened)
+  //   span_times      the timed pass's stage times
+  // Host waits of a production (untimed) round that lists every record and
+  // finds the chain linked: two -- span_link's first check, which carries the
+  // inflate's verdict, the chain's end and the list bound, and
+  // span_check_out's verdict, which carries the tail.  A failing or stopping
+  // block adds one (its status), a re-walk round or the serial link one each.
+  // A timed pass waits also in the inflate, once more in the link (nothing is
+  // queued ahead of a verdict) and in the tail.
   int decode_span_pos(uint64_t p0, uint64_t vend, ChainMode mode, bool decode, SpanDev* out);
 
   // Header bytes: inflate the first blocks until `need` stream bytes exist.
@@ -402,6 +429,61 @@ class Pipeline {
   // SoA store for n records (voff = rec_voff_) + the deferred long-key list
   int alloc_columns(uint64_t n, uint64_t stream_bytes, Columns* c, bool zero_long_n = true);
   int hip_check(hipError_t e, const char* what);
+
+  // The state of one decode_span_pos call.  It is declared once, in that
+  // function's frame, and handed to the steps by reference; it is never
+  // copied or returned by value, because rb() keeps the addresses of its
+  // fields until the next rb_sync (or rb_cancel).
+  struct SpanPass {
+    SpanPass() = default;
+    SpanPass(const SpanPass&) = delete;
+    SpanPass& operator=(const SpanPass&) = delete;
+    ChainArgs a{};
+    ChainMode mode = kReader;
+    bool dec = false;   // fill the columns and keys (reader mode)
+    // a production pass queues ahead of the verdicts it waits for (the
+    // inflate's with the link's, the list bound with the first link check,
+    // the tail with the check-out); a timed pass queues nothing early
+    bool ahead = false;
+    uint32_t k0 = 0, k1 = 0, inf_end = 0, nblk = 0;
+    Columns c{};
+    float infl_ms = 0, huff_ms = 0, lz_ms = 0, tab_ms = 0;
+    bool check_pending = false;  // the inflate's verdict lands with the next read-back
+    // the link
+    uint32_t ctr[2] = {0, 0};    // serial requests, blocks off the chain (one check round)
+    uint64_t end[2] = {0, 0};    // the max-scan's last entry, the last block's exit
+    uint64_t sm[2] = {0, 0};     // the chain's final position, != 0: it stopped there
+    uint64_t last_base = 0;      // list_offsets: base_arr_[nb - 1], cnt_[nb - 1]
+    uint32_t last_cnt = 0;
+    uint32_t ovf = 0;            // a block listed more starts than kListCap
+    bool lists = true;           // ovf == 0: the lists hold every record start
+    uint64_t bound = 0;          // the lists' records (>= the span's)
+    // the check-out / the count
+    unsigned long long need = 0; // the furthest stream byte a record needs
+    uint64_t bad = 0;            // k_rec_check_out's early-stop key (~0: none)
+    uint32_t fl[2] = {0, 0};     // its first failing block
+    uint64_t total = 0;          // the span's records
+    uint32_t first = 0xffffffffu;  // the first failing or stopping block (of [k0, k1))
+    int32_t code = 0;            // its status
+    // the tail
+    bool tail_done = false;      // queued behind k_rec_check_out, and its gate opened
+    uint64_t next = 0, voff[2] = {0, 0};  // the next record's start, first / last voff
+  };
+  bool span_range(uint64_t p0, uint64_t vend, ChainMode mode, bool decode, SpanDev* out, SpanPass& s);
+  int span_inflate(SpanPass& s);
+  int span_scratch(SpanPass& s);
+  int span_link(SpanPass& s);
+  hipError_t chain_end(SpanPass& s);
+  hipError_t list_offsets(SpanPass& s);
+  hipError_t list_bound(SpanPass& s);
+  int span_check_out(SpanPass& s);
+  int span_count(SpanPass& s);
+  bool span_grow(SpanPass& s);
+  int span_status(SpanPass& s, SpanDev* out);
+  int span_emit_walks(SpanPass& s, SpanDev* out);
+  int span_tail(SpanPass& s, uint64_t n, bool gated);
+  void span_times(const SpanPass& s);
+  void dump_off_chain(const SpanPass& s, bool list_offsets_in_base);
 
   template <typename... B>
   void own(B&... b) {

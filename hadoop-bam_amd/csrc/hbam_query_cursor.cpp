@@ -156,8 +156,12 @@ int QueryCursor::filter(BamFile& f, const SpanDev& s, HostBatch* h, bool* stop, 
   }
   QCHK(hbam::launch_query_offsets(tmp_.p, tb, flag_.p, slot_.p, klen_.p, roff_.p, n, state_.p, st));
   uint64_t v[hbam::kQueryStateWords];
-  QCHK(p.rb(v, state_.p, sizeof v, st));
-  QCHK(p.rb_sync(st));
+  hipError_t e = p.rb(v, state_.p, sizeof v, st);
+  if (e == hipSuccess) e = p.rb_sync(st);
+  if (e != hipSuccess) {
+    p.rb_cancel();  // v is a local: the queue must not keep its address
+    return hip_err(e, "read-back of the query state", err);
+  }
   if (unmapped_) {
     if (v[hbam::kQueryStop] != ~0ull) found_ = true;
   } else {

@@ -29,7 +29,8 @@ pytestmark = pytest.mark.gpu
 ALL = (1 << 64) - 1
 
 
-def test_records_after_an_eof_block_take_the_separate_launches():
+def _with_eof_stop():
+    """3,000 records, an EOF block, then 3,000 more from a block start."""
     d1, _ = synth.make_bam(3000, eof_block=True)
     d2, _ = synth.make_bam(3000, seed=99, eof_block=False)
     s2 = orc.Stream(d2)
@@ -38,7 +39,11 @@ def test_records_after_an_eof_block_take_the_separate_launches():
     # stops at the empty block (no error), and the walks list records after it
     recs = bytes(s2.data)[s2.header_end:]
     lens = [min(65280, len(recs) - a) for a in range(0, len(recs), 65280)]
-    data = d1 + orc.bgzf_compress(recs, lens, level=5, eof=True)
+    return d1 + orc.bgzf_compress(recs, lens, level=5, eof=True)
+
+
+def test_records_after_an_eof_block_take_the_separate_launches():
+    data = _with_eof_stop()
     s = orc.Stream(data)
     rc, want = s.decode_all()
     assert rc == 0 and len(want["key"]) == 3000
@@ -137,3 +142,62 @@ def test_false_start_at_a_block_start_is_rewalked(at):
         assert st["records"] == 3000 and st["status"] == 0
         assert st["first_voff"] == want["voff"][0] and st["last_voff"] == want["voff"][-1]
         assert f.splitting_index(5) == s.splitting_index(5)
+
+
+@pytest.mark.parametrize("which", ["eof_stop", "false_starts"])
+def test_timed_pass_takes_the_edge_paths(which):
+    """(d) a timed pass (timing=True) queues nothing ahead of a verdict: the
+    inflate is checked at once, the chain end and the list bound follow the
+    link check's read-back, and the tail follows k_rec_check_out's.  The
+    early stop (a) and the re-walk (c) go through those branches too."""
+    from test_gpu_windows import _digest
+    data = _with_eof_stop() if which == "eof_stop" else _with_false_start(at=(700, 1400, 2100))
+    s = orc.Stream(data)
+    rc, want = s.decode_all()
+    assert rc == 0 and len(want["key"]) == 3000
+    with hbam.BamFile(data, window_bytes=1 << 30) as f:
+        c0, r0 = f.pipeline_counters(), f.chain_counters()["rewalked"]
+        st = f.decode_span_device(f.header()["first_record_voff"], ALL, timing=True)
+        c1, r1 = f.pipeline_counters(), f.chain_counters()["rewalked"]
+        print(which, st, c0, c1, r0, r1)
+        assert st["records"] == 3000 and st["status"] == 0
+        assert st["first_voff"] == want["voff"][0] and st["last_voff"] == want["voff"][-1]
+        assert (st["key_xor"], st["voff_sum"]) == _digest(want)
+        if which == "eof_stop":
+            assert c1["records_after_stop"] > c0["records_after_stop"]
+        else:
+            assert c1["link_rewalks"] + c1["link_fallbacks"] > c0["link_rewalks"] + c0["link_fallbacks"]
+            assert r1 >= r0 + 3
+
+
+@pytest.fixture(scope="module")
+def long_reads():
+    """40 long reads in 4 KiB blocks: every record spans 4.5 to 22 blocks."""
+    d, info = synth.make_bam(40, mode="long", block_payload=4096)
+    s = orc.Stream(d)
+    rc, want = s.decode_all()
+    assert rc == 0 and len(want["key"]) == 40 and info["blocks"] > 400
+    return d, s, want
+
+
+@pytest.mark.parametrize("r", [0, 5, 17, 39])
+def test_a_record_past_the_inflated_range_goes_round_again(long_reads, r):
+    """(e) the pass inflates the span's blocks and two more; a record that
+    needs bytes beyond them (`need` > e_inf) makes it inflate up to the
+    record's end and go round again.  [voff[r], voff[r] + 1) holds record r
+    alone, which no three blocks hold."""
+    d, s, want = long_reads
+    v0, vr = int(want["voff"][0]), int(want["voff"][r])
+    for vs, n in ((vr, 1), (v0, r + 1)):
+        rc, w = s.decode_span(vs, vr + 1)
+        assert rc == 0 and len(w["key"]) == n
+        with hbam.BamFile(d, window_bytes=1 << 30) as f:
+            c0 = f.pipeline_counters()
+            assert_same_records(f.decode_span(vs, vr + 1), w)
+            launches = f.pipeline_counters()["inflate_launches"] - c0["inflate_launches"]
+            print(r, n, "inflate_launches", launches)
+            if n == 1:  # the first round's blocks, then the rest of the record's
+                assert launches >= 2
+            for timing in (False, True):
+                st = f.decode_span_device(vs, vr + 1, timing=timing)
+                assert st["records"] == n and st["status"] == 0
