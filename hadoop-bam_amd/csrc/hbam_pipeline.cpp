@@ -414,145 +414,248 @@ int Pipeline::set_ref_lengths(const std::vector<int32_t>& lens) {
   return kOk;
 }
 
+// The words of flags_.  The kernels of the scan / verify path of a locate
+// write them under these names:
+// flags_[0] = candidate count, [1] = chain break, [2] = first big ISIZE, [3] = cut tail,
+// [4] = empty blocks, [5] = anchored locate declined, [6] = its block count
+// (k_bgzf_scan takes word 0, k_bgzf_verify words 1..4, the anchor walks 5..6).
+enum LocateWord : uint32_t {
+  kLocCandidates = 0,
+  kLocChainBreak = 1,
+  kLocBigIsize = 2,  // kNoBigIsize: none
+  kLocCutTail = 3,
+  kLocEmptyBlocks = 4,
+  kLocDeclined = 5,
+  kLocAnchoredBlocks = 6,
+  kLocWords = 7
+};
+constexpr uint32_t kNoBigIsize = 0xffffffffu;
+// The serial walk zeroes the first four again and k_bgzf_walk writes them as
+// out[0..3]: the blocks it found, its status, the offset (lo, hi) where it
+// stopped -- the failing block's, or with `partial` the cut block's start.
+enum WalkWord : uint32_t { kWalkBlocks = 0, kWalkStatus = 1, kWalkAtLo = 2, kWalkAtHi = 3, kWalkWords = 4 };
+// Outside a locate, word 3 is where the first-error kernels leave the first
+// failing block (kNoBlock: none): queue_inflate_check, span_emit_walks.
+constexpr uint32_t kFirstFailWord = 3;
+
+// One locate_range call (the step map is in hbam_pipeline.h).
+struct Pipeline::LocatePass {
+  LocatePass() = default;
+  LocatePass(const LocatePass&) = delete;
+  LocatePass& operator=(const LocatePass&) = delete;
+  // the arguments
+  uint64_t lo = 0, hi = 0;
+  bool partial = false, free_start = false;
+  uint32_t nprev = 0;
+  uint64_t ubase = 0;
+  hipStream_t s = nullptr;
+  uint32_t* nnew = nullptr;   // the results: blocks appended,
+  uint64_t* tail = nullptr;   // the start of a block cut by hi
+  const uint8_t* fbase = nullptr;  // absolute file coordinates
+  uint64_t len = 0;
+  uint32_t cap = 0, walk_cap = 0;  // candidates the verify path holds; the serial walk's table bound
+  // the path so far
+  bool anchored = false;  // the anchored walks left the block starts in sorted_
+  bool serial = false;    // the serial walk has to (re)build the table
+  bool found = false;     // ... and found a chain
+  uint32_t count = 0;    // block starts in cand_ (the scan) or sorted_ (anchored)
+  // read-back words
+  uint32_t res[2] = {1, 0};          // kLocDeclined, kLocAnchoredBlocks
+  uint32_t fl[4] = {0, 0, 0, 0};     // kLocChainBreak .. kLocEmptyBlocks
+  uint64_t last = 0;                 // the last candidate (the cut tail, if any)
+  uint32_t out[kWalkWords] = {0, 0, 0, 0};
+  std::vector<uint64_t> starts;      // free start: candidates to try, in order
+  uint32_t verdict(LocateWord w) const { return fl[w - kLocChainBreak]; }
+};
+
+// The decision between the paths; the steps follow in call order.
 int Pipeline::locate_range(uint64_t lo, uint64_t hi, bool partial, bool free_start, uint32_t nprev, uint64_t ubase,
                            hipStream_t s, uint32_t* nnew, uint64_t* tail) {
   *nnew = 0;
   *tail = hi;
-  const uint8_t* fbase = dfile_ - base_;  // absolute file coordinates
-  const uint64_t len = hi - lo;
+  LocatePass p;
+  p.lo = lo;
+  p.hi = hi;
+  p.partial = partial;
+  p.free_start = free_start;
+  p.nprev = nprev;
+  p.ubase = ubase;
+  p.s = s;
+  p.nnew = nnew;
+  p.tail = tail;
+  if (int rc = locate_begin(p)) return rc;
+  // lo is a block start unless the start is free: the anchored walks first,
+  // and the scan where they do not apply or decline
+  const uint64_t nseg = locate_seg_ ? (p.len + locate_seg_ - 1) / locate_seg_ : 0;
+  if (!free_start && nseg > 0 && nseg <= 0x7fffffffu)
+    if (int rc = locate_anchored(p, (uint32_t)nseg)) return rc;
+  if (!p.anchored)
+    if (int rc = locate_scan(p)) return rc;
+  if (free_start && p.count == 0) return kOk;  // no header in the window: no blocks
+  if (p.count > 0 && p.count <= p.cap) {
+    if (int rc = locate_verify(p)) return rc;
+    if (!p.serial) return kOk;  // the chain holds: the table is in hblocks_
+  } else if (p.len > 0) {
+    p.serial = true;  // more candidates than cap, or bytes without a header (the walk has the error)
+  }
+  uint32_t n = 0;  // (an empty range: an empty table)
+  if (p.serial) {
+    if (int rc = locate_serial_walk(p)) return rc;
+    if (!p.found) return kOk;  // free start: no block chain in the window
+    n = p.out[kWalkBlocks];
+  }
+  if (int rc = locate_table(p, n)) return rc;
+  HIPCHK(rb_sync(s));
+  *nnew = n;
+  return kOk;
+}
+
+// Capacities, cand_, and flags_ zeroed (kLocBigIsize = none).  No host wait.
+int Pipeline::locate_begin(LocatePass& p) {
+  p.fbase = dfile_ - base_;
+  p.len = p.hi - p.lo;
   // candidate capacity assumes >= 1 KiB per block on average; denser files
   // (or any chain break) take the serial walk, whose table bound is len/26.
-  uint32_t cap = (uint32_t)std::min<uint64_t>(len / 1024 + 4096, 0x7fffffffu);
-  if (locate_cap_limit_) cap = std::min(cap, locate_cap_limit_);
-  const uint32_t walk_cap = (uint32_t)std::min<uint64_t>(len / 26 + 16, 0x7fffffffu);
-  HIPCHK(cand_.reserve(cap));
+  p.cap = (uint32_t)std::min<uint64_t>(p.len / 1024 + 4096, 0x7fffffffu);
+  if (locate_cap_limit_) p.cap = std::min(p.cap, locate_cap_limit_);
+  p.walk_cap = (uint32_t)std::min<uint64_t>(p.len / 26 + 16, 0x7fffffffu);
+  HIPCHK(cand_.reserve(p.cap));
   HIPCHK(flags_.reserve(8));
   // {0, 0, 0xffffffff, 0, 0} by fill kernels: a small pageable H2D can wait
   // behind other contexts' or the drop-in batches' copies on the DMA engines
-  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p), 0, 7, s));
-  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 2), -1, 1, s));
-  // flags_[0] = candidate count, [1] = chain break, [2] = first big ISIZE, [3] = cut tail,
-  // [4] = empty blocks, [5] = anchored locate declined, [6] = its block count
-  uint32_t count = 0;
-  // Anchored locate: lo is a block start, so the table is the BSIZE chain
-  // from lo.  Walks from one anchor per segment find it from the bytes around
-  // the segment boundaries and the headers; the block starts land in sorted_
-  // in file order, as the scan and the sort leave them.  Whenever the walks
-  // cannot vouch for the whole chain they decline, and the scan path below
-  // locates the range as if they had not run (its errors are the range's).
-  bool anchored = false;
-  if (!free_start && locate_seg_ && len > 0 && (len + locate_seg_ - 1) / locate_seg_ <= 0x7fffffffu) {
-    const uint32_t nseg = (uint32_t)((len + locate_seg_ - 1) / locate_seg_);
-    HIPCHK(seg_anchor_.reserve(nseg));
-    HIPCHK(seg_exit_.reserve(nseg));
-    HIPCHK(seg_cnt_.reserve(nseg));
-    HIPCHK(seg_off_.reserve(nseg));
-    HIPCHK(launch_bgzf_anchor_walk(fbase, lo, hi, locate_seg_, nseg, partial ? 1u : 0u, seg_anchor_.p, seg_exit_.p,
-                                   seg_cnt_.p, seg_off_.p, flags_.p + 5, s));
-    uint32_t res[2] = {1, 0};
-    HIPCHK(rb(res, flags_.p + 5, 8, s));
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p), 0, kLocWords, p.s));
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + kLocBigIsize), (int)kNoBigIsize, 1, p.s));
+  return kOk;
+}
+
+// Anchored locate: lo is a block start, so the table is the BSIZE chain
+// from lo.  Walks from one anchor per segment find it from the bytes around
+// the segment boundaries and the headers; the block starts land in sorted_
+// in file order, as the scan and the sort leave them.  Whenever the walks
+// cannot vouch for the whole chain they decline (counted), and the scan path
+// locates the range as if they had not run (its errors are the range's).
+// One host wait (the walks' verdict).  Leaves anchored and count.
+int Pipeline::locate_anchored(LocatePass& p, uint32_t nseg) {
+  HIPCHK(seg_anchor_.reserve(nseg));
+  HIPCHK(seg_exit_.reserve(nseg));
+  HIPCHK(seg_cnt_.reserve(nseg));
+  HIPCHK(seg_off_.reserve(nseg));
+  HIPCHK(launch_bgzf_anchor_walk(p.fbase, p.lo, p.hi, locate_seg_, nseg, p.partial ? 1u : 0u, seg_anchor_.p,
+                                 seg_exit_.p, seg_cnt_.p, seg_off_.p, flags_.p + kLocDeclined, p.s));
+  HIPCHK(rb(p.res, flags_.p + kLocDeclined, sizeof p.res, p.s));
+  HIPCHK(rb_sync(p.s));
+  if (!p.res[0] && p.res[1] > 0 && p.res[1] <= p.cap) {
+    p.count = p.res[1];
+    HIPCHK(sorted_.reserve(p.count));
+    HIPCHK(launch_bgzf_seg_emit(p.fbase, seg_anchor_.p, seg_cnt_.p, seg_off_.p, nseg, p.count, sorted_.p, p.s));
+    p.anchored = true;
+  } else {
+    ++locate_declined_;
+  }
+  return kOk;
+}
+
+// The full scan: every header candidate of [lo, hi) into cand_, unsorted.
+// One host wait (their count).
+int Pipeline::locate_scan(LocatePass& p) {
+  HIPCHK(launch_bgzf_scan(p.fbase, base_, p.lo, p.hi, cand_.p, p.cap, flags_.p + kLocCandidates, p.s));
+  HIPCHK(rb(&p.count, flags_.p + kLocCandidates, 4, p.s));
+  HIPCHK(rb_sync(p.s));
+  return kOk;
+}
+
+// The count candidates (1 .. cap) as one chain: sorts the scan's, reads a
+// free start's candidates (a host wait) and verifies from the first of them,
+// else from lo.  One host wait for the verdict, with the table behind it.
+// The chain holds: *nnew, *tail and hblocks_ are final (serial stays false);
+// it breaks: serial = true.  Counts the empty blocks and, for an anchored
+// table, locate_anchored_ / locate_declined_.
+int Pipeline::locate_verify(LocatePass& p) {
+  hipStream_t s = p.s;
+  uint32_t n = p.count;
+  HIPCHK(dblocks_.grow(p.nprev + n + 1));
+  if (!p.anchored) {
+    HIPCHK(sorted_.reserve(n));
+    size_t tmp_bytes = 0;
+    HIPCHK(sort_u64(nullptr, &tmp_bytes, cand_.p, sorted_.p, n, s));
+    HIPCHK(scan_tmp_.reserve(tmp_bytes + 16));
+    HIPCHK(sort_u64(scan_tmp_.p, &tmp_bytes, cand_.p, sorted_.p, n, s));
+  }
+  uint64_t from = p.lo;
+  if (p.free_start) {
+    p.starts.resize(std::min<uint32_t>(n, kMaxFreeStarts));
+    HIPCHK(rb(p.starts.data(), sorted_.p, p.starts.size() * 8, s));
     HIPCHK(rb_sync(s));
-    if (!res[0] && res[1] > 0 && res[1] <= cap) {
-      count = res[1];
-      HIPCHK(sorted_.reserve(count));
-      HIPCHK(launch_bgzf_seg_emit(fbase, seg_anchor_.p, seg_cnt_.p, seg_off_.p, nseg, count, sorted_.p, s));
-      anchored = true;
-    } else {
-      ++locate_declined_;
-    }
+    from = p.starts[0];
   }
-  if (!anchored) {
-    HIPCHK(launch_bgzf_scan(fbase, base_, lo, hi, cand_.p, cap, flags_.p, s));
-    HIPCHK(rb(&count, flags_.p, 4, s));
-    HIPCHK(rb_sync(s));
-  }
-  bool serial = count > cap || (count == 0 && len > 0);
-  if (free_start && count == 0) return kOk;  // no header in the window: no blocks
-  uint32_t n = serial ? 0 : count;
-  // the block table of n located blocks: ustart by a scan, read back in place
-  // into page-locked hblocks_ (the read lands at the next rb_sync)
-  auto queue_table = [&](uint32_t nt) -> int {
-    HIPCHK(dblocks_.grow(nprev + nt + 1));
-    HIPCHK(isz_.reserve(nt + 1));
-    HIPCHK(ust_.reserve(nt + 1));
-    size_t sb = 0;
-    HIPCHK(launch_block_ustart(dblocks_.p + nprev, nt, isz_.p, ust_.p, nullptr, &sb, ubase, s));
-    HIPCHK(scan_tmp_.reserve(sb + 16));
-    HIPCHK(launch_block_ustart(dblocks_.p + nprev, nt, isz_.p, ust_.p, scan_tmp_.p, &sb, ubase, s));
-    HIPCHK(hblocks_.resize(nprev + nt));
-    if (nt) HIPCHK(launch_readback(hblocks_.data() + nprev, dblocks_.p + nprev, nt * sizeof(BlockInfo), s));
-    return kOk;
-  };
-  std::vector<uint64_t> starts;  // free start: candidates to try, in order
-  if (!serial && n > 0) {
-    HIPCHK(dblocks_.grow(nprev + n + 1));
-    if (!anchored) {
-      HIPCHK(sorted_.reserve(n));
-      size_t tmp_bytes = 0;
-      HIPCHK(sort_u64(nullptr, &tmp_bytes, cand_.p, sorted_.p, n, s));
-      HIPCHK(scan_tmp_.reserve(tmp_bytes + 16));
-      HIPCHK(sort_u64(scan_tmp_.p, &tmp_bytes, cand_.p, sorted_.p, n, s));
-    }
-    if (free_start) {
-      starts.resize(std::min<uint32_t>(n, kMaxFreeStarts));
-      HIPCHK(rb(starts.data(), sorted_.p, starts.size() * 8, s));
-      HIPCHK(rb_sync(s));
-      lo = starts[0];
-    }
-    HIPCHK(launch_bgzf_verify(fbase, lo, hi, sorted_.p, n, dblocks_.p + nprev, flags_.p + 1, partial ? 1u : 0u, s));
-    uint32_t fl[4];
-    uint64_t last = 0;
-    HIPCHK(rb(fl, flags_.p + 1, 16, s));
-    HIPCHK(rb(&last, sorted_.p + n - 1, 8, s));
-    // the table queued behind the verdict as if the chain holds (a false
-    // header candidate breaks it: the serial walk below then rebuilds the
-    // table); a block cut by hi is the last entry, and the scan's entries
-    // before it do not depend on it
-    if (int rc = queue_table(n)) return rc;
-    HIPCHK(rb_sync(s));
-    if (!fl[0] && empty_blocks_ != kEmptyUnknown) empty_blocks_ += fl[3];
-    if (anchored) ++(fl[0] ? locate_declined_ : locate_anchored_);  // (the walks checked what verify checks)
-    if (fl[0]) serial = true;
-    else if (fl[1] != 0xffffffffu) return fail(kErrFormat, "BGZF block with ISIZE > 65536 (unsupported on device)");
-    else if (fl[2]) {  // the last candidate's block is cut by hi: next range
-      n -= 1;
-      *tail = last;
-    }
-    if (!serial) {
-      HIPCHK(hblocks_.resize(nprev + n));  // (drops the cut block's entry)
-      *nnew = n;
-      return kOk;
-    }
-  }
-  if (serial) {
-    empty_blocks_ = kEmptyUnknown;  // (the walk does not count them)
-    uint32_t out[4];
-    HIPCHK(dblocks_.grow(nprev + walk_cap + 1));
-    if (starts.empty()) starts.push_back(lo);
-    bool found = false;
-    for (size_t j = 0; j < starts.size() && !found; ++j) {
-      HIPCHK(hipMemsetAsync(flags_.p, 0, 16, s));
-      HIPCHK(launch_bgzf_walk(fbase, starts[j], hi, dblocks_.p + nprev, walk_cap, flags_.p, partial ? 1u : 0u, s));
-      HIPCHK(rb(out, flags_.p, 16, s));
-      HIPCHK(rb_sync(s));
-      n = out[0];
-      const uint64_t at = (uint64_t)out[2] | ((uint64_t)out[3] << 32);
-      if (out[1] != kOk) {
-        if (free_start) continue;  // a false header candidate: try the next one
-        return fail((int)out[1], "malformed BGZF block at offset " + std::to_string(at));
-      }
-      if (free_start && n == 0) continue;
-      if (partial) *tail = at;
-      found = true;
-    }
-    if (!found) {
-      if (free_start) return kOk;  // no block chain in the window
-      return fail(kErrFormat, "malformed BGZF block");
-    }
-  }
-  if (int rc = queue_table(n)) return rc;
+  HIPCHK(launch_bgzf_verify(p.fbase, from, p.hi, sorted_.p, n, dblocks_.p + p.nprev, flags_.p + kLocChainBreak,
+                            p.partial ? 1u : 0u, s));
+  HIPCHK(rb(p.fl, flags_.p + kLocChainBreak, sizeof p.fl, s));
+  HIPCHK(rb(&p.last, sorted_.p + n - 1, 8, s));
+  // the table queued behind the verdict as if the chain holds (a false
+  // header candidate breaks it: the serial walk then rebuilds the table); a
+  // block cut by hi is the last entry, and the scan's entries before it do
+  // not depend on it
+  if (int rc = locate_table(p, n)) return rc;
   HIPCHK(rb_sync(s));
-  *nnew = n;
+  const bool broken = p.verdict(kLocChainBreak) != 0;
+  if (!broken && empty_blocks_ != kEmptyUnknown) empty_blocks_ += p.verdict(kLocEmptyBlocks);
+  if (p.anchored) ++(broken ? locate_declined_ : locate_anchored_);  // (the walks checked what verify checks)
+  if (broken) {
+    p.serial = true;
+    return kOk;
+  }
+  if (p.verdict(kLocBigIsize) != kNoBigIsize)
+    return fail(kErrFormat, "BGZF block with ISIZE > 65536 (unsupported on device)");
+  if (p.verdict(kLocCutTail)) {  // the last candidate's block is cut by hi: next range
+    n -= 1;
+    *p.tail = p.last;
+  }
+  HIPCHK(hblocks_.resize(p.nprev + n));  // (drops the cut block's entry)
+  *p.nnew = n;
+  return kOk;
+}
+
+// The serial BSIZE walk from lo -- or, free start, from each candidate of
+// verify in turn until one chains to the end (a false header candidate fails
+// or finds nothing).  One host wait per start tried.  Leaves found and out
+// (kWalkBlocks = the table's size) and, with `partial`, *tail.
+int Pipeline::locate_serial_walk(LocatePass& p) {
+  empty_blocks_ = kEmptyUnknown;  // (the walk does not count them)
+  HIPCHK(dblocks_.grow(p.nprev + p.walk_cap + 1));
+  if (p.starts.empty()) p.starts.push_back(p.lo);
+  for (size_t j = 0; j < p.starts.size() && !p.found; ++j) {
+    HIPCHK(hipMemsetAsync(flags_.p, 0, kWalkWords * sizeof(uint32_t), p.s));
+    HIPCHK(launch_bgzf_walk(p.fbase, p.starts[j], p.hi, dblocks_.p + p.nprev, p.walk_cap, flags_.p,
+                            p.partial ? 1u : 0u, p.s));
+    HIPCHK(rb(p.out, flags_.p, sizeof p.out, p.s));
+    HIPCHK(rb_sync(p.s));
+    const uint64_t at = (uint64_t)p.out[kWalkAtLo] | ((uint64_t)p.out[kWalkAtHi] << 32);
+    if (p.out[kWalkStatus] != kOk) {
+      if (p.free_start) continue;  // a false header candidate: try the next one
+      return fail((int)p.out[kWalkStatus], "malformed BGZF block at offset " + std::to_string(at));
+    }
+    if (p.free_start && p.out[kWalkBlocks] == 0) continue;
+    if (p.partial) *p.tail = at;
+    p.found = true;
+  }
+  if (!p.found && !p.free_start) return fail(kErrFormat, "malformed BGZF block");
+  return kOk;
+}
+
+// The block table of n located blocks: ustart by a scan, read back in place
+// into page-locked hblocks_ (the read lands at the next rb_sync).  No host wait.
+int Pipeline::locate_table(LocatePass& p, uint32_t n) {
+  HIPCHK(dblocks_.grow(p.nprev + n + 1));
+  BlockInfo* blocks = dblocks_.p + p.nprev;
+  HIPCHK(isz_.reserve(n + 1));
+  HIPCHK(ust_.reserve(n + 1));
+  size_t sb = 0;
+  HIPCHK(launch_block_ustart(blocks, n, isz_.p, ust_.p, nullptr, &sb, p.ubase, p.s));
+  HIPCHK(scan_tmp_.reserve(sb + 16));
+  HIPCHK(launch_block_ustart(blocks, n, isz_.p, ust_.p, scan_tmp_.p, &sb, p.ubase, p.s));
+  HIPCHK(hblocks_.resize(p.nprev + n));
+  if (n) HIPCHK(launch_readback(hblocks_.data() + p.nprev, blocks, n * sizeof(BlockInfo), p.s));
   return kOk;
 }
 
@@ -620,9 +723,28 @@ int Pipeline::run_streamed(const uint8_t* data, uint64_t len, uint64_t piece, ui
   HIPCHK(hipSetDevice(device_));
   if (int rc = stage_wait()) return rc;  // no staged copy in flight over the window being replaced
   piece = std::max<uint64_t>(piece, 1ull << 20);
-  const uint64_t np = std::max<uint64_t>(1, (len + piece - 1) / piece);
-  // capacity up front, so that nothing reallocates under queued work (grow()
-  // still handles a file that outruns the estimates, at the cost of a wait)
+  if (int rc = streamed_reserve(len, piece)) return rc;
+  HIPCHK(hipEventRecord(ev_[6], stream_copy_));
+  uint32_t nb = 0;
+  if (int rc = streamed_pieces(data, len, piece, &nb)) return rc;
+  window_end_ = base_ + len;
+  int rc = finish_blocks();  // (the inflates: ordered before stream_'s next work)
+  if (rc != kOk) return rc;
+  HIPCHK(queue_inflate_check(0, nb));
+  HIPCHK(rb_sync(stream_));
+  if ((rc = inflate_verdict(0, nb)) != kOk) return rc;
+  rc = decode_span(voff_of(first_pos), ~0ull, kReader, true, out);
+  if (rc != kOk) return rc;
+  HIPCHK(hipEventRecord(ev_[7], stream_));
+  HIPCHK(hipEventSynchronize(ev_[7]));
+  HIPCHK(hipEventElapsedTime(ms, ev_[6], ev_[7]));
+  return kOk;
+}
+
+// Capacity up front, so that nothing reallocates under queued work (grow()
+// still handles a file that outruns the estimates, at the cost of a wait).
+// Waits for the pipeline's streams.
+int Pipeline::streamed_reserve(uint64_t len, uint64_t piece) {
   HIPCHK(dblocks_.grow(len / 16384 + 4096));
   HIPCHK(hout_.grow(len / 16384 + 4096));
   HIPCHK(du_.grow(std::max<uint64_t>(total_u_, 4 * len) + kUPad));
@@ -635,18 +757,25 @@ int Pipeline::run_streamed(const uint8_t* data, uint64_t len, uint64_t piece, ui
   }
   HIPCHK(pstats_.reserve(kPathStatWords));
   HIPCHK(streams_.sync());
+  return kOk;
+}
 
-  // Piece k's copy and its locate run in order on stream_copy_, the inflate
-  // of located blocks on the inflate streams.  (With locate on its own stream,
-  // which shares a hardware queue with stream_ at GPU_MAX_HW_QUEUES = 4, every
-  // locate waited behind the queued inflates: copy and decode serialized.)
-  auto queue_copy = [&](uint64_t k) -> int {
-    const uint64_t o = k * piece, sz = std::min(piece, len - o);
-    HIPCHK(hipMemcpyAsync(dfile_ + o, data + o, sz, hipMemcpyHostToDevice, stream_copy_));
-    return kOk;
-  };
-  HIPCHK(hipEventRecord(ev_[6], stream_copy_));
-  if (int rc0 = queue_copy(0)) return rc0;
+// piece k of the file on its way to HBM, on stream_copy_
+int Pipeline::streamed_copy(const uint8_t* data, uint64_t len, uint64_t piece, uint64_t k) {
+  const uint64_t o = k * piece, sz = std::min(piece, len - o);
+  HIPCHK(hipMemcpyAsync(dfile_ + o, data + o, sz, hipMemcpyHostToDevice, stream_copy_));
+  return kOk;
+}
+
+// Piece k's copy and its locate run in order on stream_copy_, the inflate
+// of located blocks on the inflate streams.  (With locate on its own stream,
+// which shares a hardware queue with stream_ at GPU_MAX_HW_QUEUES = 4, every
+// locate waited behind the queued inflates: copy and decode serialized.)
+// Host waits: each piece's locate.  *nblocks = the blocks located, every one
+// handed to inflate.
+int Pipeline::streamed_pieces(const uint8_t* data, uint64_t len, uint64_t piece, uint32_t* nblocks) {
+  const uint64_t np = std::max<uint64_t>(1, (len + piece - 1) / piece);
+  if (int rc0 = streamed_copy(data, len, piece, 0)) return rc0;
   hblocks_.clear();
   inflated_.clear();
   empty_blocks_ = 0;
@@ -660,7 +789,7 @@ int Pipeline::run_streamed(const uint8_t* data, uint64_t len, uint64_t piece, ui
     uint64_t tail = hi;
     int rc = locate_range(lo, hi, !last, false, nb, total_u_, stream_copy_, &nnew, &tail);
     if (rc != kOk) return rc;
-    if (!last && (rc = queue_copy(k + 1)) != kOk) return rc;  // on the wire while piece k inflates
+    if (!last && (rc = streamed_copy(data, len, piece, k + 1)) != kOk) return rc;  // on the wire while piece k inflates
     if (nnew) {
       const BlockInfo& e = hblocks_[nb + nnew - 1];
       total_u_ = e.ustart + e.isize;
@@ -672,57 +801,80 @@ int Pipeline::run_streamed(const uint8_t* data, uint64_t len, uint64_t piece, ui
     // inflate in launches of >= kStreamInflateBlocks blocks: a piece's few
     // thousand blocks alone would leave most CUs idle in each round's tail
     if (nb > queued && (nb - queued >= kStreamInflateBlocks || last)) {
-      rc = inflate(queued, nb, true, false, false);  // (phase B beside the next piece's phase A)
+      rc = inflate(queued, nb, InflateMode::kStreamed);  // (phase B beside the next piece's phase A)
       if (rc != kOk) return rc;
       queued = nb;
     }
     lo = tail;
   }
-  window_end_ = base_ + len;
-  int rc = finish_blocks();  // (the inflates: ordered before stream_'s next work)
-  if (rc != kOk) return rc;
-  HIPCHK(flags_.reserve(4));
-  const uint32_t none = 0xffffffffu;
-  uint32_t first = none;
-  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 3), (int)none, 1, stream_));
-  HIPCHK(launch_first_error_hout(hout_.p, 0, nb, flags_.p + 3, stream_));
-  HIPCHK(rb(&first, flags_.p + 3, 4, stream_));
-  HIPCHK(rb_sync(stream_));
-  if (first != none) {
-    HuffOut ho;
-    HIPCHK(rb(&ho, hout_.p + first, sizeof ho, stream_));
-    HIPCHK(rb_sync(stream_));
-    std::fill(inflated_.begin(), inflated_.end(), 0);
-    const char* what = ho.status == kErrFormat ? "Did not inflate expected amount" : "invalid DEFLATE data";
-    return fail(ho.status, std::string(what) + " in BGZF block at offset " + std::to_string(hblocks_[first].coff));
-  }
-  rc = decode_span(voff_of(first_pos), ~0ull, kReader, true, out);
-  if (rc != kOk) return rc;
-  HIPCHK(hipEventRecord(ev_[7], stream_));
-  HIPCHK(hipEventSynchronize(ev_[7]));
-  HIPCHK(hipEventElapsedTime(ms, ev_[6], ev_[7]));
+  *nblocks = nb;
   return kOk;
 }
 
-int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool join) {
-  HIPCHK(hipSetDevice(device_));
-  inflate_queued_ = false;
-  const uint32_t nblk = (uint32_t)hblocks_.size();
-  b1 = std::min(b1, nblk);
-  if (b0 >= b1) return kOk;
-  const uint8_t* fbase = dfile_ - base_;
-  if (timing) HIPCHK(hipEventRecord(ev_[2], stream_));
-  // Chunks of up to kInflateChunkBlocks blocks: per chunk the table build and
-  // phase A in rounds, then phase B.  Production runs overlap them: phase A
-  // on stream_, phase B on stream_b_ after it, the round-0 tables of chunk j
-  // on stream_t_ beside phase A of chunk j-1, token and table buffers by
-  // chunk parity (~0.7 ms per C2 pass faster than one stream).  A timed run
-  // (measurement) puts every launch on stream_, each bracketed by events, so
-  // its per-kernel times are kernel durations, as rocprofv3 reports them.
-  const bool serial = timing;
-  hipStream_t sB = serial ? stream_ : stream_b_, sT = serial ? stream_ : stream_t_;
+// One inflate call (the step map, with the stream of every launch, is in
+// hbam_pipeline.h).  Chunks of up to kInflateChunkBlocks blocks: per chunk
+// the table build and phase A in rounds, then phase B.  Production runs
+// overlap them: phase A on stream_, phase B on stream_b_ after it, the
+// round-0 tables of chunk j on stream_t_ beside phase A of chunk j-1, token
+// and table buffers by chunk parity (~0.7 ms per C2 pass faster than one
+// stream).  A timed run (measurement) puts every launch on stream_, each
+// bracketed by events, so its per-kernel times are kernel durations, as
+// rocprofv3 reports them.
+struct Pipeline::InflatePass {
+  InflatePass() = default;
+  InflatePass(const InflatePass&) = delete;
+  InflatePass& operator=(const InflatePass&) = delete;
+  uint32_t b0 = 0, b1 = 0;
+  const uint8_t* fbase = nullptr;
+  bool serial = false;  // a timed pass: one stream, one set of buffers, events around every launch
+  bool join = true;     // the last chunk's phase B on stream_ itself
   struct Chunk { uint32_t b, e; };
   std::vector<Chunk> chunks;
+  size_t ne = 0;  // events recorded (serial)
+  float tab_ms = 0, huff_ms = 0, lz_ms = 0;
+};
+
+int Pipeline::inflate(uint32_t b0, uint32_t b1, InflateMode mode) {
+  HIPCHK(hipSetDevice(device_));
+  inflate_queued_ = false;
+  b1 = std::min(b1, (uint32_t)hblocks_.size());
+  if (b0 >= b1) return kOk;
+  if (timing) HIPCHK(hipEventRecord(ev_[2], stream_));
+  InflatePass p;
+  p.b0 = b0;
+  p.b1 = b1;
+  p.fbase = dfile_ - base_;
+  p.serial = timing;
+  p.join = mode != InflateMode::kStreamed;
+  inflate_plan(p, mode == InflateMode::kStreamed);
+  if (p.chunks.empty()) {
+    times.inflate = times.huff = times.lz77 = times.tables = 0;
+    return kOk;
+  }
+  if (int rc = inflate_reserve(p)) return rc;
+  for (size_t j = 0; j < p.chunks.size(); ++j)
+    if (int rc = inflate_chunk(p, j)) return rc;
+  if (int rc = inflate_join(p)) return rc;
+  if (timing)
+    if (int rc = inflate_times(p)) return rc;
+  inflate_queued_ = true;
+  if (mode != InflateMode::kChecked) return kOk;  // the caller checks hout_ once all blocks are queued
+  HIPCHK(queue_inflate_check(b0, b1));
+  if (timing) HIPCHK(hipEventRecord(ev_[3], stream_));
+  HIPCHK(rb_sync(stream_));
+  if (timing) {
+    (void)hipEventElapsedTime(&times.inflate, ev_[2], ev_[3]);
+    times.tables = p.tab_ms;
+    times.huff = p.huff_ms;
+    times.lz77 = p.lz_ms;
+  }
+  return inflate_verdict(b0, b1);
+}
+
+// The chunks of [b0, b1), without the blocks inflated already unless `force`.
+// Host code only; reads inflated_.
+void Pipeline::inflate_plan(InflatePass& p, bool force) {
+  const uint32_t b0 = p.b0, b1 = p.b1;
   // (the GPU is idle here: the common case -- nothing of [b0, b1) inflated
   // yet -- is planned without a walk over the blocks)
   const bool fresh = force || std::find(inflated_.begin() + b0, inflated_.begin() + b1, (uint8_t)1) ==
@@ -737,11 +889,16 @@ int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool joi
     uint32_t e = b;
     if (fresh) e = std::min(b1, b + per);
     else while (e < b1 && e - b < per && !inflated_[e]) ++e;
-    chunks.push_back({b, e});
+    p.chunks.push_back({b, e});
     b = e;
   }
-  const bool any = !chunks.empty();
-  const size_t nc = chunks.size();
+}
+
+// A timed pass's events; every buffer for the largest chunk, one set or (the
+// chunks overlap) one per parity; pstats_ zeroed on stream_; the fork of
+// stream_b_ and stream_t_ off stream_.  No host wait unless a buffer grows.
+int Pipeline::inflate_reserve(InflatePass& p) {
+  const size_t nc = p.chunks.size();
   const size_t per_chunk = 2 * (2 * kInflateRounds + 1);  // event pairs: tables + phase A per round, phase B
   if (timing && tev_.size() < per_chunk * nc) {
     const size_t old = tev_.size();
@@ -751,119 +908,127 @@ int Pipeline::inflate(uint32_t b0, uint32_t b1, bool force, bool check, bool joi
   // size every buffer up front: a reallocation inside the loop could free a
   // token buffer that phase B of an earlier chunk is still reading
   uint64_t max_u = 64, max_nb = 0;
-  for (const Chunk& c : chunks) {
+  for (const InflatePass::Chunk& c : p.chunks) {
     max_u = std::max(max_u, hblocks_[c.e - 1].ustart + hblocks_[c.e - 1].isize - hblocks_[c.b].ustart);
     max_nb = std::max<uint64_t>(max_nb, c.e - c.b);
   }
-  const int nbuf = nc > 1 && !serial ? 2 : 1;
-  if (any) {
-    for (int i = 0; i < nbuf; ++i) {
-      HIPCHK(tokens_[i].reserve(max_u + 16));  // phase B reads tokens as uint4
-      HIPCHK(tables_[i].reserve(max_nb * kHuffTableImage));
-      HIPCHK(tinfo_[i].reserve(max_nb));
-      HIPCHK(flist_[i].reserve(huff_list_words(max_nb)));
-    }
-    HIPCHK(pstats_.reserve(kPathStatWords));
-    HIPCHK(hipMemsetAsync(pstats_.p, 0, kPathStatWords * sizeof(uint32_t), stream_));
-    if (!serial) {  // phase B and the table builds see everything queued on stream_ before this call
-      HIPCHK(hipEventRecord(sync_ev_[0], stream_));
-      HIPCHK(hipStreamWaitEvent(stream_b_, sync_ev_[0], 0));
-      HIPCHK(hipStreamWaitEvent(stream_t_, sync_ev_[0], 0));
-    }
+  const int nbuf = nc > 1 && !p.serial ? 2 : 1;
+  for (int i = 0; i < nbuf; ++i) {
+    HIPCHK(tokens_[i].reserve(max_u + 16));  // phase B reads tokens as uint4
+    HIPCHK(tables_[i].reserve(max_nb * kHuffTableImage));
+    HIPCHK(tinfo_[i].reserve(max_nb));
+    HIPCHK(flist_[i].reserve(huff_list_words(max_nb)));
   }
-  size_t ne = 0;  // events recorded (serial)
-  auto mark = [&]() -> hipError_t { return serial ? hipEventRecord(tev_[ne++], stream_) : hipSuccess; };
-  for (size_t j = 0; j < nc; ++j) {
-    const uint32_t cb = chunks[j].b, ce = chunks[j].e;
-    const int par = serial ? 0 : (int)(j & 1);
-    const uint64_t cu = hblocks_[cb].ustart;
-    if (!serial && j >= 2) {
-      HIPCHK(hipStreamWaitEvent(stream_, sync_ev_[2 + par], 0));  // B(j-2) released the token buffer
-      HIPCHK(hipStreamWaitEvent(stream_t_, hdone_ev_[par], 0));   // A(j-2) released the table buffer
+  HIPCHK(pstats_.reserve(kPathStatWords));
+  HIPCHK(hipMemsetAsync(pstats_.p, 0, kPathStatWords * sizeof(uint32_t), stream_));
+  if (!p.serial) {  // phase B and the table builds see everything queued on stream_ before this call
+    // (sync_ev_[0] serves twice: here as the fork, then as "phase A of an
+    // even chunk done" in inflate_chunk.  The two waits below are queued
+    // before it is recorded again, and a wait holds the record it was queued on.)
+    HIPCHK(hipEventRecord(sync_ev_[0], stream_));
+    HIPCHK(hipStreamWaitEvent(stream_b_, sync_ev_[0], 0));
+    HIPCHK(hipStreamWaitEvent(stream_t_, sync_ev_[0], 0));
+  }
+  return kOk;
+}
+
+hipError_t Pipeline::inflate_mark(InflatePass& p) {
+  return p.serial ? hipEventRecord(tev_[p.ne++], stream_) : hipSuccess;
+}
+
+// Chunk j: the waits on chunk j-2 (same parity, same buffers), the list's
+// zero, per round tables + phase A, then phase B; marks its blocks inflated.
+// No host wait.
+int Pipeline::inflate_chunk(InflatePass& p, size_t j) {
+  const size_t nc = p.chunks.size();
+  const uint32_t cb = p.chunks[j].b, ce = p.chunks[j].e;
+  const bool serial = p.serial;
+  const int par = serial ? 0 : (int)(j & 1);
+  const uint64_t cu = hblocks_[cb].ustart;
+  // The stream of the round-0 tables and of phase B; everything else, and
+  // all of a timed pass, runs on stream_.
+  // (the first chunk's round-0 tables run on stream_ itself: nothing runs
+  // beside them, and a cross-stream wait costs ~15 us at the pass's start)
+  const bool t_own = !serial && j > 0;
+  // the last chunk's phase B on stream_ itself: nothing of this call is
+  // left to overlap it, and the chain after it then needs no cross-stream wait
+  const bool b_own = !serial && (j + 1 < nc || !p.join);
+  hipStream_t sT = t_own ? stream_t_ : stream_, sB = b_own ? stream_b_ : stream_;
+  if (!serial && j >= 2) {
+    HIPCHK(hipStreamWaitEvent(stream_, sync_ev_[2 + par], 0));  // B(j-2) released the token buffer
+    HIPCHK(hipStreamWaitEvent(stream_t_, hdone_ev_[par], 0));   // A(j-2) released the table buffer
+  }
+  // (the list is written and read on stream_ only: the chunk of the same
+  // parity before this one is done with it)
+  HIPCHK(hipMemsetAsync(flist_[par].p, 0, kHuffListHdr * sizeof(uint32_t), stream_));
+  // rounds: each decode stops a block before its next DEFLATE header, which
+  // the next round's table build parses (the last round decodes inline)
+  for (uint32_t r = 0; r < kInflateRounds; ++r) {
+    HIPCHK(inflate_mark(p));
+    HIPCHK(launch_huff_tables(p.fbase, dblocks_.p, cb, ce - cb, tables_[par].p, tinfo_[par].p, hout_.p, r,
+                              r == 0 ? sT : stream_));
+    HIPCHK(inflate_mark(p));
+    if (r == 0 && t_own) {
+      HIPCHK(hipEventRecord(tab_ev_[par], stream_t_));
+      HIPCHK(hipStreamWaitEvent(stream_, tab_ev_[par], 0));
     }
-    // rounds: each decode stops a block before its next DEFLATE header, which
-    // the next round's table build parses (the last round decodes inline)
-    // (the first chunk's round-0 tables run on stream_ itself: nothing runs
-    // beside them, and a cross-stream wait costs ~15 us at the pass's start)
-    const bool t_own = !serial && j > 0;
-    // (the list is written and read on stream_ only: the chunk of the same
-    // parity before this one is done with it)
-    HIPCHK(hipMemsetAsync(flist_[par].p, 0, kHuffListHdr * sizeof(uint32_t), stream_));
-    for (uint32_t r = 0; r < kInflateRounds; ++r) {
-      HIPCHK(mark());
-      HIPCHK(launch_huff_tables(fbase, dblocks_.p, cb, ce - cb, tables_[par].p, tinfo_[par].p, hout_.p, r,
-                                r == 0 && t_own ? sT : stream_));
-      HIPCHK(mark());
-      if (r == 0 && t_own) {
-        HIPCHK(hipEventRecord(tab_ev_[par], stream_t_));
-        HIPCHK(hipStreamWaitEvent(stream_, tab_ev_[par], 0));
-      }
-      HIPCHK(mark());
-      HIPCHK(launch_inflate_huff_prebuilt(fbase, dblocks_.p, cb, ce - cb, cu, tokens_[par].p, hout_.p,
-                                          tables_[par].p, tinfo_[par].p, r, r + 1 < kInflateRounds ? 1u : 0u,
-                                          flist_[par].p, pstats_.p, stream_));
-      HIPCHK(mark());
-    }
-    // the last chunk's phase B on stream_ itself: nothing of this call is
-    // left to overlap it, and the chain after it then needs no cross-stream wait
-    const bool b_own = !serial && (j + 1 < nc || !join);
-    hipStream_t sBj = b_own ? sB : stream_;
-    if (!serial) HIPCHK(hipEventRecord(hdone_ev_[par], stream_));
-    if (b_own) {
-      HIPCHK(hipEventRecord(sync_ev_[par], stream_));
-      HIPCHK(hipStreamWaitEvent(stream_b_, sync_ev_[par], 0));
-    }
-    HIPCHK(mark());
-    HIPCHK(launch_inflate_lz77(dblocks_.p, cb, ce - cb, cu, tokens_[par].p, hout_.p, du_.p, sBj));
-    HIPCHK(mark());
-    if (!serial) HIPCHK(hipEventRecord(sync_ev_[2 + par], sBj));
-    std::fill(inflated_.begin() + cb, inflated_.begin() + ce, (uint8_t)1);
-    ++inflate_launches_;
+    HIPCHK(inflate_mark(p));
+    HIPCHK(launch_inflate_huff_prebuilt(p.fbase, dblocks_.p, cb, ce - cb, cu, tokens_[par].p, hout_.p,
+                                        tables_[par].p, tinfo_[par].p, r, r + 1 < kInflateRounds ? 1u : 0u,
+                                        flist_[par].p, pstats_.p, stream_));
+    HIPCHK(inflate_mark(p));
   }
-  if (any && !serial) {  // everything after this call on stream_ sees phase B done
-    if (!join) HIPCHK(hipStreamWaitEvent(stream_, sync_ev_[2 + ((nc - 1) & 1)], 0));  // (with join it ran on stream_)
-    if (nc >= 2) HIPCHK(hipStreamWaitEvent(stream_, sync_ev_[2 + ((nc - 2) & 1)], 0));
+  if (!serial) HIPCHK(hipEventRecord(hdone_ev_[par], stream_));
+  if (b_own) {
+    HIPCHK(hipEventRecord(sync_ev_[par], stream_));
+    HIPCHK(hipStreamWaitEvent(stream_b_, sync_ev_[par], 0));
   }
-  float tab_ms = 0, huff_ms = 0, lz_ms = 0;
-  if (timing && any) {
-    HIPCHK(hipEventSynchronize(tev_[ne - 1]));
-    for (size_t i = 0; i < ne; i += 2) {
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, tev_[i], tev_[i + 1]);
-      const size_t k = (i / 2) % (2 * kInflateRounds + 1);  // position of the pair within its chunk
-      (k == 2 * kInflateRounds ? lz_ms : (k & 1) ? huff_ms : tab_ms) += ms;
-    }
+  HIPCHK(inflate_mark(p));
+  HIPCHK(launch_inflate_lz77(dblocks_.p, cb, ce - cb, cu, tokens_[par].p, hout_.p, du_.p, sB));
+  HIPCHK(inflate_mark(p));
+  if (!serial) HIPCHK(hipEventRecord(sync_ev_[2 + par], sB));
+  std::fill(inflated_.begin() + cb, inflated_.begin() + ce, (uint8_t)1);
+  ++inflate_launches_;
+  return kOk;
+}
+
+// Everything after this call on stream_ sees phase B done: stream_ waits for
+// the phase Bs that ran on stream_b_ and that no later chunk waited for (the
+// last two chunks').
+int Pipeline::inflate_join(InflatePass& p) {
+  if (p.serial) return kOk;
+  const size_t nc = p.chunks.size();
+  if (!p.join) HIPCHK(hipStreamWaitEvent(stream_, sync_ev_[2 + ((nc - 1) & 1)], 0));  // (with join it ran on stream_)
+  if (nc >= 2) HIPCHK(hipStreamWaitEvent(stream_, sync_ev_[2 + ((nc - 2) & 1)], 0));
+  return kOk;
+}
+
+// A timed pass: waits for the last event; the kernel times per launch kind.
+int Pipeline::inflate_times(InflatePass& p) {
+  HIPCHK(hipEventSynchronize(tev_[p.ne - 1]));
+  for (size_t i = 0; i < p.ne; i += 2) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, tev_[i], tev_[i + 1]);
+    const size_t k = (i / 2) % (2 * kInflateRounds + 1);  // position of the pair within its chunk
+    (k == 2 * kInflateRounds ? p.lz_ms : (k & 1) ? p.huff_ms : p.tab_ms) += ms;
   }
-  if (!any) {
-    times.inflate = times.huff = times.lz77 = times.tables = 0;
-    return kOk;
-  }
-  inflate_queued_ = true;
-  if (!check) return kOk;  // the caller checks hout_ once all blocks are queued
-  HIPCHK(queue_inflate_check(b0, b1));
-  if (timing) HIPCHK(hipEventRecord(ev_[3], stream_));
-  HIPCHK(rb_sync(stream_));
-  if (timing) {
-    (void)hipEventElapsedTime(&times.inflate, ev_[2], ev_[3]);
-    times.tables = tab_ms;
-    times.huff = huff_ms;
-    times.lz77 = lz_ms;
-  }
-  return inflate_verdict(b0, b1);
+  return kOk;
 }
 
 hipError_t Pipeline::queue_inflate_check(uint32_t b0, uint32_t b1) {
+  infl_first_ = kNoBlock;
   hipError_t e = flags_.reserve(4);
-  if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 3), -1, 1, stream_);
-  if (e == hipSuccess) e = launch_first_error_hout(hout_.p, b0, b1 - b0, flags_.p + 3, stream_);
-  infl_first_ = 0xffffffffu;
-  if (e == hipSuccess) e = rb(&infl_first_, flags_.p + 3, 4, stream_);
+  if (e != hipSuccess) return e;
+  uint32_t* first = flags_.p + kFirstFailWord;
+  e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(first), (int)kNoBlock, 1, stream_);
+  if (e == hipSuccess) e = launch_first_error_hout(hout_.p, b0, b1 - b0, first, stream_);
+  if (e == hipSuccess) e = rb(&infl_first_, first, 4, stream_);
   return e;
 }
 
 int Pipeline::inflate_verdict(uint32_t b0, uint32_t b1) {
   const uint32_t first = infl_first_;
-  if (first == 0xffffffffu) return kOk;
+  if (first == kNoBlock) return kOk;
   HuffOut ho;
   HIPCHK(rb(&ho, hout_.p + b0 + first, sizeof ho, stream_));
   HIPCHK(rb_sync(stream_));
@@ -1024,7 +1189,7 @@ bool Pipeline::span_range(uint64_t p0, uint64_t vend, ChainMode mode, bool decod
 // fewer; the chain kernels take any bytes, and their results are not used
 // before the verdict).  No host wait of its own.
 int Pipeline::span_inflate(SpanPass& s) {
-  const int rc = inflate(s.k0, s.inf_end, false, !s.ahead);
+  const int rc = inflate(s.k0, s.inf_end, s.ahead ? InflateMode::kQueued : InflateMode::kChecked);
   s.check_pending = false;
   if (rc == kOk && s.ahead && inflate_queued_) {
     HIPCHK(queue_inflate_check(s.k0, s.inf_end));
@@ -1339,12 +1504,13 @@ int Pipeline::span_status(SpanPass& s, SpanDev* out) {
 int Pipeline::span_emit_walks(SpanPass& s, SpanDev* out) {
   ChainArgs& a = s.a;
   const uint32_t nb = a.k1 - a.k0;
-  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags_.p + 3), (int)kNoBlock, 1, stream_));
-  HIPCHK(launch_first_error_i32(errv_.p, nb, flags_.p + 3, stream_));
-  HIPCHK(rb(&s.first, flags_.p + 3, 4, stream_));
+  uint32_t* first = flags_.p + kFirstFailWord;
+  HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(first), (int)kNoBlock, 1, stream_));
+  HIPCHK(launch_first_error_i32(errv_.p, nb, first, stream_));
+  HIPCHK(rb(&s.first, first, 4, stream_));
   HIPCHK(rb_sync(stream_));
   if (int rc = span_status(s, out)) return rc;
-  if (s.first != kNoBlock) HIPCHK(launch_truncate_counts(cnt_.p, nb, flags_.p + 3, stream_));
+  if (s.first != kNoBlock) HIPCHK(launch_truncate_counts(cnt_.p, nb, first, stream_));
   HIPCHK(list_offsets(s));
   HIPCHK(rb_sync(stream_));
   s.total = s.last_base + s.last_cnt;

@@ -180,6 +180,15 @@ hipError_t create_stream(hipStream_t* s, StreamLevel level);
 // hadoopbam.samheaderreader.validation-stringency property).
 enum Stringency : int { kStrict = 0, kLenient = 1, kSilent = 2 };
 
+// What one Pipeline::inflate call does besides queueing the chunks:
+//   kChecked   checks the DEFLATE status of [b0, b1) and waits for it (one host wait)
+//   kQueued    leaves the work queued, no host wait: the caller checks later
+//              (span_inflate: queue_inflate_check, the verdict with the link's read-back)
+//   kStreamed  kQueued, and: every block of [b0, b1) is inflated whether marked
+//              or not, and the last chunk's phase B stays on the phase-B stream,
+//              beside what is queued next (run_streamed: the next piece's phase A)
+enum class InflateMode { kChecked, kQueued, kStreamed };
+
 // Anchored locate: bytes per segment (the S sweep)
 #ifndef HBAM_LOCATE_SEG_BYTES
 #define HBAM_LOCATE_SEG_BYTES (512u << 10)
@@ -250,6 +259,33 @@ class Pipeline {
   // blocks that end inside it.  free_start: the window may begin inside a
   // block (split-guess windows); the block chain starts at the first header
   // candidate whose BSIZE chain runs to the window end.
+  // locate() is locate_range over the whole window, then finish_blocks;
+  // run_streamed calls locate_range per piece.  locate_range decides between
+  // the paths below; its steps share one LocatePass (private, defined in
+  // hbam_pipeline.cpp beside the names of flags_' words), in this order:
+  //   locate_begin        capacities, cand_, flags_ zeroed
+  //   locate_anchored     (lo is a block start, locate_seg_ != 0) k_bgzf_anchor_walk, its
+  //                       verdict; accepted: k_bgzf_seg_emit into sorted_; else counted declined
+  //   locate_scan         (no anchored table) k_bgzf_scan, the candidate count
+  //   locate_verify       (1 .. cap candidates) the sort unless anchored, a free start's
+  //                       candidates, k_bgzf_verify, locate_table queued behind its verdict;
+  //                       accepts the table (the cut tail dropped) or asks for the serial walk
+  //   locate_serial_walk  (more candidates than cap, none in a range with bytes, or a
+  //                       broken chain) k_bgzf_walk from lo, or from each free-start
+  //                       candidate in turn; its error texts; then locate_table
+  //   locate_table        ustart by a scan, the table read back in place into hblocks_
+  // Host waits of one range (production and timed alike; every one is an rb_sync):
+  //   anchored, accepted            2  the walks' verdict; verify's verdict with the table
+  //   scan, accepted                2  the candidate count; verify's verdict with the table
+  //   anchored declined, then scan  3  both of the above counts, then verify's
+  //   free start, accepted          3  the count; the candidates to try; verify's
+  //   serial walk                   the waits up to it (1 from the scan's count, 2 or 3
+  //                                 through a verify that found the chain broken), then 1
+  //                                 per candidate tried (one candidate unless free start)
+  //                                 and 1 for the table
+  // A free start with no header candidate ends after the count (1); a buffer
+  // that has to grow waits for the streams besides.  A timed locate() adds one
+  // event wait.  finish_blocks waits for nothing.
   int locate(bool free_start = false);
   const HostTable<BlockInfo>& blocks() const { return hblocks_; }
   uint64_t total_u() const { return total_u_; }
@@ -257,11 +293,42 @@ class Pipeline {
   // file offset just past the last located block (where the next window starts)
   uint64_t window_end() const { return window_end_; }
 
-  // Inflate blocks [b0, b1) into the contiguous inflated stream.  check =
-  // false leaves the work queued (no DEFLATE error check, no host wait).
-  // join: the last chunk's phase B runs on stream() itself (the caller's next
-  // work needs it); else on the phase-B stream, beside what is queued next.
-  int inflate(uint32_t b0, uint32_t b1, bool force = false, bool check = true, bool join = true);
+  // Inflate blocks [b0, b1) into the contiguous inflated stream (InflateMode,
+  // above: what else the call does).  The steps share one InflatePass
+  // (private, defined in hbam_pipeline.cpp), in this order:
+  //   inflate_plan     chunks of [b0, b1): even, at most kInflateChunkBlocks blocks each,
+  //                    without the blocks inflated already (kStreamed: every block); host only
+  //   inflate_reserve  a timed pass's events; token / table / info / list buffers for one
+  //                    parity (two when chunks overlap); pstats_ and its zero; the fork
+  //   inflate_chunk    per chunk j, parity par = j & 1: the waits on chunk j - 2, the list's
+  //                    zero, per round tables + phase A, then phase B
+  //   inflate_join     stream() waits for the phase Bs that ran beside it
+  //   inflate_times    (timed) waits for the last event; the sums per launch kind
+  //   kChecked only:   queue_inflate_check, rb_sync, inflate_verdict -- the one place
+  //                    the DEFLATE error text is produced, for every caller
+  // Streams of a production (untimed) pass, s = stream(), sB = the phase-B
+  // stream, sT = the table stream (sB and sT wait for a fork event on s first):
+  //   zero of pstats_, of a chunk's list      s
+  //   tables, round 0                         first chunk: s; every later chunk: sT, and s
+  //                                           waits for them (tab_ev_[par])
+  //   tables, later rounds                    s
+  //   phase A, every round                    s
+  //   phase B                                 first and middle chunks: sB, after phase A
+  //                                           (sync_ev_[par]); the last chunk (the only
+  //                                           one, too): s -- but sB under kStreamed, which
+  //                                           does not join
+  //   chunk j >= 2                            s waits for phase B of chunk j - 2 (its token
+  //                                           buffer: sync_ev_[2 + par]); sT for phase A of
+  //                                           chunk j - 2 (its tables: hdone_ev_[par])
+  //   the join                                s waits for phase B of the last chunk but one
+  //                                           and, under kStreamed, of the last one
+  // A timed pass (timing = true) puts every launch on s, in the order above,
+  // each between two events of its own, with one set of buffers and none of
+  // the cross-stream events.
+  // Host waits: kChecked one (the verdict's rb_sync; a failing block's status
+  // one more), kQueued and kStreamed none.  A timed pass adds one (the last
+  // event) in every mode.  A buffer that has to grow waits for the streams.
+  int inflate(uint32_t b0, uint32_t b1, InflateMode mode = InflateMode::kChecked);
 
   // End-to-end pass from host memory: the file (same length as the loaded
   // one) is copied to HBM in pieces on a copy stream while the BGZF blocks of
@@ -419,11 +486,34 @@ class Pipeline {
   // *tail = its start (hi when none).
   int locate_range(uint64_t lo, uint64_t hi, bool partial, bool free_start, uint32_t nprev, uint64_t ubase,
                    hipStream_t s, uint32_t* nnew, uint64_t* tail);
+  // The state of one locate_range call / one inflate call: like SpanPass
+  // below, declared once in that function's frame and handed to the steps by
+  // reference (rb() keeps the addresses of LocatePass's fields).  The step
+  // maps are above locate() and inflate().
+  struct LocatePass;
+  int locate_begin(LocatePass& p);
+  int locate_anchored(LocatePass& p, uint32_t nseg);
+  int locate_scan(LocatePass& p);
+  int locate_verify(LocatePass& p);
+  int locate_serial_walk(LocatePass& p);
+  int locate_table(LocatePass& p, uint32_t n);
   int finish_blocks();  // total_u_, dead positions, pads, per-block state after locate
+  struct InflatePass;
+  void inflate_plan(InflatePass& p, bool force);
+  int inflate_reserve(InflatePass& p);
+  int inflate_chunk(InflatePass& p, size_t j);
+  int inflate_join(InflatePass& p);
+  int inflate_times(InflatePass& p);
+  hipError_t inflate_mark(InflatePass& p);  // a timed pass's next event, on stream_
   // the first failing block of [b0, b1)'s inflate, read back into
   // infl_first_ at the next rb_sync; inflate_verdict: its error, if any
   hipError_t queue_inflate_check(uint32_t b0, uint32_t b1);
   int inflate_verdict(uint32_t b0, uint32_t b1);
+  // run_streamed's seams: capacity up front; per piece copy, locate and
+  // inflate (*nblocks = the blocks located); the check and the decode stay in it
+  int streamed_reserve(uint64_t len, uint64_t piece);
+  int streamed_copy(const uint8_t* data, uint64_t len, uint64_t piece, uint64_t k);
+  int streamed_pieces(const uint8_t* data, uint64_t len, uint64_t piece, uint32_t* nblocks);
   uint32_t infl_first_ = 0xffffffffu;
   bool inflate_queued_ = false;  // the last inflate() queued any chunk
   // SoA store for n records (voff = rec_voff_) + the deferred long-key list

@@ -5,9 +5,13 @@ the parity tests pin against the oracle) and to the oracle itself."""
 import numpy as np
 import pytest
 
+import deflate_cases as dc
 import hbam
+import locate_cases as lc
 import orc
 from hbam import synth
+from test_gpu_inflate_lean import gunzip_block
+from test_gpu_inflate_shapes import STATUS, block
 
 pytestmark = pytest.mark.gpu
 
@@ -48,3 +52,65 @@ def test_streamed_matches_resident_and_oracle(kw, piece):
     assert rc == 0
     np.testing.assert_array_equal(k1, want["key"])
     np.testing.assert_array_equal(v1, want["voff"])
+
+
+# ---- a DEFLATE error in a later piece: one verdict for the resident and the streamed pass
+def _short_of_isize(cid):
+    """A valid case of deflate_cases under a footer ISIZE one byte larger than
+    its stream holds: [htsjdk] BlockGunzipper's "Did not inflate expected
+    amount".  (deflate_cases.INVALID has no case of that status: zlib refuses
+    every one of its streams.)"""
+    c = dc.get(cid)
+    assert c.want == "OK" and c.isize < 65536
+    return c._replace(id=cid + "+1", out=None, isize=c.isize + 1, want="E_FORMAT")
+
+
+BAD_BLOCKS = {
+    "M2": ("E_IO", "invalid DEFLATE data", lambda: dc.get("M2")),
+    "S3+1": ("E_FORMAT", "Did not inflate expected amount", lambda: _short_of_isize("S3")),
+}
+assert "M2" in dc.INVALID
+
+
+@pytest.fixture(scope="module")
+def two_pieces():
+    """A BAM of more than two 1 MiB pieces, its oracle keys and the end of the
+    first block that starts in the second piece."""
+    data, _ = synth.make_bam(17000)
+    assert len(data) > (2 << 20)
+    starts = lc.block_starts(data)
+    k = next(i for i, p in enumerate(starts) if p >= (1 << 20))
+    assert starts[k + 1] < (2 << 20)
+    rc, want = orc.Stream(data).decode_all()
+    assert rc == 0
+    return data, want["key"], starts[k + 1]
+
+
+@pytest.mark.parametrize("cid", list(BAD_BLOCKS))
+def test_deflate_error_in_second_piece(cid, two_pieces):
+    want, text, make = BAD_BLOCKS[cid]
+    c = make()
+    assert c.want == want and gunzip_block(c.cdata, c.isize)[0] == STATUS[want]
+    good, keys, at = two_pieces
+    bad = np.frombuffer(good[:at] + block(c) + good[at:], np.uint8)
+    msg = "%s in BGZF block at offset %d" % (text, at)
+    g = hbam.Gpu(0)
+    buf = hbam.PinnedBuffer(bad.nbytes)
+    try:
+        g.load(bad)
+        buf.array[:] = bad
+        with pytest.raises(hbam.HbamError) as resident:
+            g.run()
+        with pytest.raises(hbam.HbamError) as streamed:
+            g.run_streamed(buf.ptr, bad.nbytes, 1 << 20)
+        print("resident: %s\nstreamed: %s" % (resident.value, streamed.value))
+        assert resident.value.code == streamed.value.code == STATUS[want]
+        assert str(resident.value) == str(streamed.value) == "%s: %s" % (hbam.ERROR_NAMES[STATUS[want]], msg)
+        # the failed passes leave no block marked inflated: the good file decodes
+        g.load(good)
+        st = g.run()
+        assert st["status"] == 0 and st["records"] == len(keys)
+        np.testing.assert_array_equal(g.fetch(st["records"])[0], keys)
+    finally:
+        buf.close()
+        g.close()
