@@ -1,28 +1,20 @@
-// hbam_abi.cpp -- extern "C" boundary (include/hbam.h) over the C++ mirror.
-#include "../../include/hbam.h"
-
-#include <hip/hip_runtime.h>
-
+// hbam_abi.cpp -- extern "C" boundary (include/hbam.h) over the C++ mirror:
+// the product API, everything on hbam_ctx and the calls that take no handle.
+// The device-resident decode (hbam_gpu) is hbam_abi_gpu.cpp.
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
+#include <initializer_list>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
+#include "hbam_abi_util.h"
 #include "hbam_deflate_api.h"
 #include "hbam_mem.h"
-#include "hbam_host.h"
 #include "hbam_launch.h"
 #include "hbam_merge.h"
 
+using namespace hbam_abi;
 using hadoop_bam::BAMInputFormat;
-using hadoop_bam::BamFile;
 using hadoop_bam::BAMRecordReader;
-using hadoop_bam::Carry;
 using hadoop_bam::FileSplit;
 using hadoop_bam::FileVirtualSplit;
 using hadoop_bam::HostBatch;
@@ -30,7 +22,19 @@ using hadoop_bam::OpenOptions;
 using hadoop_bam::QueryCursor;
 using hadoop_bam::SpanCursor;
 using hadoop_bam::SplittingBAMIndexer;
-using hadoop_bam::Step;
+
+// Where the ctx's last batch came from: what hbam_encode_writables,
+// hbam_sort_writables, hbam_format_sam and hbam_reader_position may serve.
+//   kNone       no batch (a fresh ctx), or the span batch was forgotten
+//   kSpan       hbam_decode_span handed it out (its result may still be an error or several windows:
+//               the cursor knows)
+//   kQuery      hbam_query_next handed it out
+//   kWritables  hbam_decode_writables handed it out
+// The one transition besides those three calls: a call that moves the ctx's
+// window (reset_cursors: hbam_file_stats, hbam_prefetch, hbam_query_intervals,
+// hbam_decode_span_device, the index, guess and split calls, ...) takes kSpan
+// to kNone.  kQuery and kWritables stay until the next of the three calls.
+enum class LastBatch { kNone, kSpan, kQuery, kWritables };
 
 struct hbam_ctx {
   std::unique_ptr<BamFile> f;
@@ -40,10 +44,8 @@ struct hbam_ctx {
   HostBatch wbatch;     // the columns of the last hbam_decode_writables
   hadoop_bam::BatchView batch;  // the last batch handed out (cursor slots or wbatch)
   hbam::SpanDev wspan;  // device result of the last hbam_decode_writables
-  bool last_is_writables = false;
+  LastBatch last = LastBatch::kNone;
   std::unique_ptr<QueryCursor> query;  // the open bounded traversal (hbam_query_*), if any
-  bool last_is_query = false;          // the last batch came from hbam_query_next
-  bool has_span_batch = false;         // an hbam_decode_span batch is the ctx's last (hbam_format_sam asks)
   std::unique_ptr<hbam::Merger> merge;  // the open merge (hbam_merge_*), if any (destroyed first: its buffers
                                         // wait for the pipeline's streams)
 };
@@ -51,28 +53,14 @@ struct hbam_ctx {
 // Forget the split and the query being read: the call about to run moves the
 // ctx's window.
 static void reset_cursors(hbam_ctx* ctx) {
-  ctx->has_span_batch = false;
+  if (ctx->last == LastBatch::kSpan) ctx->last = LastBatch::kNone;
   ctx->cursor.reset();
   ctx->query.reset();
 }
 
-struct hbam_gpu {
-  std::unique_ptr<BamFile> f;
-  int device = 0;
-  uint64_t window = hadoop_bam::kDefaultWindowBytes;
-  int stringency = HBAM_STRICT;  // of the next hbam_gpu_load
-  std::string err;
-  hbam::SpanDev span;  // last window of the last run
-  hbam::DevBuf<uint8_t> enc;  // hbam_gpu_encode_writables output
-  uint64_t enc_bytes = 0;
-  std::unique_ptr<hbam::BgzfCompressor> bgzf;  // hbam_gpu_bgzf_compress
-};
+thread_local std::string hbam_abi::g_open_err;
 
 namespace {
-// the last error of a call with no ctx (open, compress, codec): per thread,
-// as JNI callers from many executor threads read it right after their call
-thread_local std::string g_open_err;
-
 OpenOptions options_of(const hbam_opts* opts, bool header) {
   hbam_opts o{};
   if (opts) o = *opts;
@@ -126,120 +114,68 @@ void fill_batch(const hadoop_bam::BatchView& h, hbam_batch* out) {
   out->data_len = h.data_len;
 }
 
-// The decode of FileVirtualSplit [vstart, vend) window by window with the
-// records left in HBM; stats accumulate over windows.  *last = the last
-// window's span (C2-sized files: the whole split).
-int decode_device(BamFile& f, uint64_t vstart, uint64_t vend, int32_t flags, hbam_gpu_stats* st,
-                  hbam::SpanDev* last, std::string* err) {
-  memset(st, 0, sizeof *st);
-  hbam::Pipeline& p = f.pipe();
-  p.timing = (flags & 1) != 0;
-  const bool decode = (flags & 2) == 0, digest = (flags & 4) != 0;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, p.stream());
-  const uint64_t lf0 = p.link_fallbacks(), il0 = p.inflate_launches(), lr0 = p.link_rewalks();
-  const uint64_t rf0 = p.record_fallbacks();
-  f.invalidate_window();  // a timed pass locates and inflates afresh
-  Carry c{vstart >> 16, vstart & 0xffff};
-  bool cont = false;
-  int rc = HBAM_OK;
-  bool first = true;
-  // Windows read from the host ramp up (SpanCursor::ramp_window: 32 MiB,
-  // doubling to the full window), so that decoding starts after the first
-  // small copy instead of a whole 4 GiB window's (C3 from the mapped file);
-  // a span already in HBM decodes in full windows.
-  const uint64_t span_end = std::min<uint64_t>(f.file_size(), vend == ~0ull ? ~0ull : (vend >> 16) + 0x20000);
-  const bool ramp = !f.window_explicit() && !f.resident(vstart >> 16, span_end);
-  uint64_t nwin = 0;
-  for (;;) {
-    Step step;
-    rc = ramp ? f.decode_step(c, vend, hbam::kReader, decode, cont, &step,
-                              hadoop_bam::SpanCursor::ramp_window(f.window_bytes(), nwin),
-                              hadoop_bam::SpanCursor::ramp_window(f.window_bytes(), nwin + 1))
-              : f.decode_step(c, vend, hbam::kReader, decode, cont, &step);
-    ++nwin;
-    if (rc != HBAM_OK) {
-      *err = f.error();
-      break;
-    }
-    const hbam::SpanDev& s = step.span;
-    st->windows += 1;
-    st->records += s.n;
-    st->n_blocks += p.blocks().size();
-    // bytes of this window up to the block the next window starts at (it
-    // starts at the record this one could not finish): each counted once
-    const bool last_window = step.ended || step.status != HBAM_OK;
-    const int64_t next_u = last_window ? -1 : p.pos_of_voff(step.next.coff << 16);
-    if (next_u < 0) {
-      st->compressed_bytes += p.window_end() - c.coff;
-      st->inflated_bytes += p.total_u();
-    } else {
-      st->compressed_bytes += step.next.coff - c.coff;
-      st->inflated_bytes += (uint64_t)next_u;
-    }
-    if (p.timing) {
-      st->ms_locate += p.times.locate;
-      st->ms_inflate += p.times.inflate;
-      st->ms_huff += p.times.huff;
-      st->ms_lz77 += p.times.lz77;
-      st->ms_tables += p.times.tables;
-      st->ms_chain += p.times.chain;
-      st->ms_decode += p.times.decode;
-    }
-    if (s.n) {
-      if (first) st->first_voff = s.first_voff;
-      st->last_voff = s.last_voff;
-      first = false;
-      if (digest) {
-        uint64_t dg[4];
-        hbam::SpanDev d = s;
-        if (!decode) d.col.key = nullptr;
-        rc = p.span_digest(d, dg);
-        if (rc != HBAM_OK) {
-          *err = p.error();
-          break;
-        }
-        st->key_xor ^= dg[0];
-        st->voff_sum += dg[1];
-        uint64_t w = 1, b = HBAM_DIGEST_P;  // P^n of this window's records
-        for (uint64_t e = s.n; e; e >>= 1, b *= b)
-          if (e & 1) w *= b;
-        st->key_digest = st->key_digest * w + dg[2];
-        st->voff_digest = st->voff_digest * w + dg[3];
-      }
-    }
-    if (last) *last = s;
-    if (step.status != HBAM_OK) {
-      st->status = step.status;
-      *err = step.error;
-      break;
-    }
-    if (step.ended) break;
-    c = step.next;
-    cont = true;
+bool valid_sort_order(int order) {
+  return order == HBAM_SORT_KEY || order == HBAM_SORT_COORDINATE || order == HBAM_SORT_QUERYNAME;
+}
+
+// the ctx's pipeline: its file's, else the codec's; null when it has neither
+hbam::Pipeline* pipe_of(hbam_ctx* ctx) { return !ctx ? nullptr : ctx->f ? &ctx->f->pipe() : ctx->codec.get(); }
+
+// The one rule of what hbam_encode_writables, hbam_sort_writables and
+// hbam_format_sam (`who`) serve: the ctx's last batch, if hbam_decode_span
+// handed it out and its records lie in one window in HBM (*span).
+// need_span_batch: refuse kNone too.  True only for hbam_format_sam: the two
+// encodings of a ctx that has no batch (n = 0) are empty and are served.
+int batch_span_or_state_error(hbam_ctx* ctx, const char* who, bool need_span_batch, hbam::SpanDev* span) {
+  const bool from_span = ctx->last == LastBatch::kSpan || (ctx->last == LastBatch::kNone && !need_span_batch);
+  if (from_span && (!ctx->batch.n || ctx->cursor.last_batch_span(span))) return HBAM_OK;
+  ctx->err = std::string(who) + " needs a one-window batch from hbam_decode_span";
+  return HBAM_E_STATE;
+}
+
+// ---- the spine of the three batch-to-bytes calls ------------------------------
+int check_cap(hbam_ctx* ctx, uint64_t cap, uint64_t bytes, const char* what) {
+  if (cap >= bytes) return HBAM_OK;
+  ctx->err = std::string("output buffer too small for the ") + what;
+  return HBAM_E_ARG;
+}
+
+struct D2H {  // one copy back to the caller (dst NULL: not asked for)
+  void* dst;
+  const void* src;
+  uint64_t bytes;
+};
+
+// queues the copies on the pipeline's stream and waits for them once
+int copy_back(hbam_ctx* ctx, hipStream_t s, std::initializer_list<D2H> copies) {
+  hipError_t e = hipSuccess;
+  for (const D2H& c : copies)
+    if (e == hipSuccess && c.dst) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && hipStreamSynchronize(s) == hipSuccess) return HBAM_OK;
+  ctx->err = "hipMemcpy D2H failed";
+  return HBAM_E_DEVICE;
+}
+
+// `bytes` of output for the caller: a device buffer of that size rounded up to
+// 16, launch(buffer, more) writes it and names up to two further arrays that
+// its kernels left in the pipeline; then out and those are copied back.
+// alloc_text / alloc_code: what the call answers when the buffer cannot be had
+// (the encodings and the SAM text differ, and stay so).
+template <class Launch>
+int write_and_copy_back(hbam_ctx* ctx, hbam::Pipeline& p, uint8_t* out, uint64_t bytes, const char* alloc_text,
+                        int alloc_code, Launch launch) {
+  hbam::DevBuf<uint8_t> dst(&p.streams());
+  if (dst.reserve((bytes + 15) & ~15ull) != hipSuccess) {
+    ctx->err = alloc_text;
+    return alloc_code;
   }
-  (void)hipEventRecord(e1, p.stream());
-  (void)hipEventSynchronize(e1);
-  (void)hipEventElapsedTime(&st->ms_total, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  st->link_fallbacks = (int32_t)(p.link_fallbacks() - lf0);
-  st->inflate_launches = (int32_t)(p.inflate_launches() - il0);
-  st->link_rewalks = (int32_t)(p.link_rewalks() - lr0);
-  st->record_fallbacks = (int32_t)(p.record_fallbacks() - rf0);
-  if (rc != HBAM_OK) st->status = rc;
-  return rc != HBAM_OK ? rc : st->status;
-}
-// page-locked blocks handed out by hbam_host_alloc and their sizes (pinned_free needs them)
-std::mutex& host_alloc_mu() {
-  static std::mutex* m = new std::mutex();
-  return *m;
-}
-std::map<void*, size_t>& host_allocs() {
-  static std::map<void*, size_t>* m = new std::map<void*, size_t>();
-  return *m;
+  D2H more[2] = {};
+  const int rc = launch(dst.p, more);
+  if (rc != HBAM_OK) {
+    ctx->err = p.error();
+    return rc;
+  }
+  return copy_back(ctx, p.stream(), {{out, dst.p, bytes}, more[0], more[1]});
 }
 
 }  // namespace
@@ -318,10 +254,7 @@ int hbam_bgzf_compress(const hbam_opts* opts, const void* data, uint64_t len, co
       lens.push_back((uint32_t)std::min<uint64_t>((uint64_t)block_size, len - pos));
     }
   }
-  if (o.device < 0 || o.device >= hbam_device_count()) {
-    g_open_err = "no HIP device " + std::to_string(o.device);
-    return HBAM_E_DEVICE;
-  }
+  if (check_device(o.device) != HBAM_OK) return HBAM_E_DEVICE;
   if (hipSetDevice(o.device) != hipSuccess) return HBAM_E_DEVICE;
   hipStream_t s;
   if (hipStreamCreate(&s) != hipSuccess) return HBAM_E_DEVICE;
@@ -413,10 +346,8 @@ int hbam_prefetch(hbam_ctx* ctx, uint64_t lo, uint64_t hi) {
 int hbam_decode_span(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, uint64_t max_records, hbam_batch* out) {
   memset(out, 0, sizeof *out);
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  ctx->last_is_writables = false;
-  ctx->last_is_query = false;
+  ctx->last = LastBatch::kSpan;
   ctx->query.reset();  // a split read ends an open query
-  ctx->has_span_batch = true;
   uint64_t next = vend;
   int rc = ctx->cursor.next_batch(*ctx->f, vstart, vend, max_records, &ctx->batch, &next, &ctx->err);
   fill_batch(ctx->batch, out);
@@ -454,8 +385,7 @@ int hbam_query_next(hbam_ctx* ctx, uint64_t max_records, hbam_batch* out) {
     ctx->err = "hbam_query_next needs an open query (hbam_query_intervals / hbam_query_unmapped)";
     return HBAM_E_STATE;
   }
-  ctx->last_is_writables = false;
-  ctx->last_is_query = true;
+  ctx->last = LastBatch::kQuery;
   const int rc = ctx->query->next_batch(*ctx->f, max_records, &ctx->batch, &ctx->err);
   fill_batch(ctx->batch, out);
   out->status = rc;
@@ -466,7 +396,7 @@ int hbam_query_next(hbam_ctx* ctx, uint64_t max_records, hbam_batch* out) {
 int hbam_reader_position(hbam_ctx* ctx, uint64_t i, uint64_t* pos) {
   *pos = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  if (ctx->last_is_writables || ctx->last_is_query || !ctx->cursor.valid()) {
+  if (ctx->last != LastBatch::kSpan || !ctx->cursor.valid()) {
     ctx->err = "hbam_reader_position needs the last call on the ctx to be hbam_decode_span";
     return HBAM_E_STATE;
   }
@@ -489,23 +419,10 @@ int hbam_pipeline_counters(hbam_ctx* ctx, uint64_t out[5]) {
   return HBAM_OK;
 }
 
-namespace {
-void set_locate(BamFile& f, uint64_t seg_bytes, uint32_t cap_limit) {
-  hbam::Pipeline& p = f.pipe();
-  if (seg_bytes == HBAM_LOCATE_SEG_DEFAULT) {
-    seg_bytes = hbam::kLocateSegBytes;
-    if (const char* e = getenv("HBAM_LOCATE_SEG")) seg_bytes = strtoull(e, nullptr, 0);
-  }
-  p.set_locate(seg_bytes, cap_limit);
-  f.invalidate_window();
-}
-}  // namespace
-
 int hbam_locate_counters(hbam_ctx* ctx, uint64_t out[2]) {
   out[0] = out[1] = 0;
   if (!ctx || !ctx->f) return HBAM_E_STATE;
-  out[0] = ctx->f->pipe().locate_anchored();
-  out[1] = ctx->f->pipe().locate_declined();
+  locate_counters(ctx->f->pipe(), out);
   return HBAM_OK;
 }
 
@@ -549,10 +466,7 @@ int hbam_open_codec(const hbam_opts* opts, hbam_ctx** out) {
   *out = nullptr;
   hbam_opts o{};
   if (opts) o = *opts;
-  if (o.device < 0 || o.device >= hbam_device_count()) {
-    g_open_err = "no HIP device " + std::to_string(o.device);
-    return HBAM_E_DEVICE;
-  }
+  if (check_device(o.device) != HBAM_OK) return HBAM_E_DEVICE;
   auto* c = new hbam_ctx();
   c->codec.reset(new hbam::Pipeline(o.device));
   *out = c;
@@ -568,12 +482,10 @@ int hbam_encode_writables(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* o
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   hbam::Pipeline& p = ctx->f->pipe();
   hbam::SpanDev span;
-  if (ctx->last_is_writables || ctx->last_is_query || (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
-    ctx->err = "hbam_encode_writables needs a one-window batch from hbam_decode_span";
-    return HBAM_E_STATE;
-  }
+  int rc = batch_span_or_state_error(ctx, "hbam_encode_writables", false, &span);
+  if (rc != HBAM_OK) return rc;
   uint64_t bytes = 0;
-  int rc = ctx->batch.n ? p.encoded_bytes(span, &bytes) : HBAM_OK;
+  rc = ctx->batch.n ? p.encoded_bytes(span, &bytes) : HBAM_OK;
   if (rc != HBAM_OK) {
     ctx->err = p.error();
     return rc;
@@ -585,27 +497,9 @@ int hbam_encode_writables(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* o
     offs[h.n] = bytes;
   }
   if (!out) return HBAM_OK;
-  if (cap < bytes) {
-    ctx->err = "output buffer too small for the encoded records";
-    return HBAM_E_ARG;
-  }
-  if (bytes == 0) return HBAM_OK;
-  hbam::DevBuf<uint8_t> dst(&p.streams());
-  if (dst.reserve((bytes + 15) & ~15ull) != hipSuccess) {
-    ctx->err = "hipMalloc failed";
-    return HBAM_E_DEVICE;
-  }
-  rc = p.encode_writables(span, bytes, dst.p);
-  if (rc != HBAM_OK) {
-    ctx->err = p.error();
-    return rc;
-  }
-  if (hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, p.stream()) != hipSuccess ||
-      hipStreamSynchronize(p.stream()) != hipSuccess) {
-    ctx->err = "hipMemcpy D2H failed";
-    return HBAM_E_DEVICE;
-  }
-  return HBAM_OK;
+  if ((rc = check_cap(ctx, cap, bytes, "encoded records")) != HBAM_OK || bytes == 0) return rc;
+  return write_and_copy_back(ctx, p, out, bytes, "hipMalloc failed", HBAM_E_DEVICE,
+                             [&](uint8_t* dst, D2H*) { return p.encode_writables(span, bytes, dst); });
 }
 
 int hbam_format_sam(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, uint64_t* len) {
@@ -613,11 +507,8 @@ int hbam_format_sam(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, u
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   hbam::Pipeline& p = ctx->f->pipe();
   hbam::SpanDev span;
-  if (!ctx->has_span_batch || ctx->last_is_writables || ctx->last_is_query ||
-      (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
-    ctx->err = "hbam_format_sam needs a one-window batch from hbam_decode_span";
-    return HBAM_E_STATE;
-  }
+  int rc = batch_span_or_state_error(ctx, "hbam_format_sam", true, &span);
+  if (rc != HBAM_OK) return rc;
   const uint64_t n = ctx->batch.n;
   if (n == 0) {
     if (offs) offs[0] = 0;
@@ -628,7 +519,7 @@ int hbam_format_sam(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, u
     return HBAM_E_ARG;
   }
   uint64_t bytes = 0, bad = ~0ull;
-  int rc = p.set_sam_refs(ctx->f->ref_names());
+  rc = p.set_sam_refs(ctx->f->ref_names());
   if (rc == HBAM_OK) rc = p.sam_measure(span, &bytes, &bad);
   if (rc != HBAM_OK) {
     ctx->err = p.error();
@@ -639,32 +530,12 @@ int hbam_format_sam(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, u
     return HBAM_E_FORMAT;
   }
   *len = bytes;
-  if (offs && (hipMemcpyAsync(offs, p.sam_offsets(), (n + 1) * 8, hipMemcpyDeviceToHost, p.stream()) != hipSuccess ||
-               hipStreamSynchronize(p.stream()) != hipSuccess)) {
-    ctx->err = "hipMemcpy D2H failed";
-    return HBAM_E_DEVICE;
-  }
+  // the line starts go back with the size query too
+  if (offs && (rc = copy_back(ctx, p.stream(), {{offs, p.sam_offsets(), (n + 1) * 8}})) != HBAM_OK) return rc;
   if (!out) return HBAM_OK;
-  if (cap < bytes) {
-    ctx->err = "output buffer too small for the SAM text";
-    return HBAM_E_ARG;
-  }
-  hbam::DevBuf<uint8_t> dst(&p.streams());
-  if (dst.reserve((bytes + 15) & ~15ull) != hipSuccess) {
-    ctx->err = "device allocation of the SAM text failed";
-    return HBAM_E_NOMEM;
-  }
-  rc = p.sam_write(span, bytes, dst.p);
-  if (rc != HBAM_OK) {
-    ctx->err = p.error();
-    return rc;
-  }
-  if (hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, p.stream()) != hipSuccess ||
-      hipStreamSynchronize(p.stream()) != hipSuccess) {
-    ctx->err = "hipMemcpy D2H failed";
-    return HBAM_E_DEVICE;
-  }
-  return HBAM_OK;
+  if ((rc = check_cap(ctx, cap, bytes, "SAM text")) != HBAM_OK) return rc;
+  return write_and_copy_back(ctx, p, out, bytes, "device allocation of the SAM text failed", HBAM_E_NOMEM,
+                             [&](uint8_t* dst, D2H*) { return p.sam_write(span, bytes, dst); });
 }
 
 int hbam_sort_writables(hbam_ctx* ctx, int32_t order, uint8_t* out, uint64_t cap, uint64_t* offs, uint32_t* perm,
@@ -673,11 +544,9 @@ int hbam_sort_writables(hbam_ctx* ctx, int32_t order, uint8_t* out, uint64_t cap
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   hbam::Pipeline& p = ctx->f->pipe();
   hbam::SpanDev span;
-  if (ctx->last_is_writables || ctx->last_is_query || (ctx->batch.n && !ctx->cursor.last_batch_span(&span))) {
-    ctx->err = "hbam_sort_writables needs a one-window batch from hbam_decode_span";
-    return HBAM_E_STATE;
-  }
-  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE && order != HBAM_SORT_QUERYNAME) {
+  int rc = batch_span_or_state_error(ctx, "hbam_sort_writables", false, &span);
+  if (rc != HBAM_OK) return rc;
+  if (!valid_sort_order(order)) {
     ctx->err = "unknown sort order " + std::to_string(order);
     return HBAM_E_ARG;
   }
@@ -692,43 +561,26 @@ int hbam_sort_writables(hbam_ctx* ctx, int32_t order, uint8_t* out, uint64_t cap
   for (uint64_t i = 0; i < n; ++i) bytes += h.rest_len[i];
   *len = bytes;
   if (!out) return HBAM_OK;
-  if (cap < bytes) {
-    ctx->err = "output buffer too small for the encoded records";
-    return HBAM_E_ARG;
-  }
+  if ((rc = check_cap(ctx, cap, bytes, "encoded records")) != HBAM_OK) return rc;
   if (n == 0) {
     if (offs) offs[0] = 0;
     return HBAM_OK;
   }
-  hbam::DevBuf<uint8_t> dst(&p.streams());
-  if (dst.reserve((bytes + 15) & ~15ull) != hipSuccess) {
-    ctx->err = "hipMalloc failed";
-    return HBAM_E_DEVICE;
-  }
-  const int rc = p.sort_writables(span, order, bytes, dst.p);
-  if (rc != HBAM_OK) {
-    ctx->err = p.error();
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(out, dst.p, bytes, hipMemcpyDeviceToHost, p.stream());
-  if (e == hipSuccess && offs)
-    e = hipMemcpyAsync(offs, p.sort_offsets(), (n + 1) * 8, hipMemcpyDeviceToHost, p.stream());
-  if (e == hipSuccess && perm) e = hipMemcpyAsync(perm, p.sort_perm(), n * 4, hipMemcpyDeviceToHost, p.stream());
-  if (e != hipSuccess || hipStreamSynchronize(p.stream()) != hipSuccess) {
-    ctx->err = "hipMemcpy D2H failed";
-    return HBAM_E_DEVICE;
-  }
-  return HBAM_OK;
+  return write_and_copy_back(ctx, p, out, bytes, "hipMalloc failed", HBAM_E_DEVICE, [&](uint8_t* dst, D2H* more) {
+    const int r = p.sort_writables(span, order, bytes, dst);
+    more[0] = {offs, p.sort_offsets(), (n + 1) * 8};  // all three copies, then one wait
+    more[1] = {perm, p.sort_perm(), n * 4};
+    return r;
+  });
 }
 
 int hbam_decode_writables(hbam_ctx* ctx, const void* buf, uint64_t len, const uint64_t* offs, uint64_t n,
                           hbam_batch* out) {
   memset(out, 0, sizeof *out);
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
-  hbam::Pipeline& p = ctx->f ? ctx->f->pipe() : *ctx->codec;
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
+  hbam::Pipeline& p = *pipe_of(ctx);
   reset_cursors(ctx);
-  ctx->last_is_writables = true;
-  ctx->last_is_query = false;
+  ctx->last = LastBatch::kWritables;
   hbam::SpanDev& span = ctx->wspan;
   span = hbam::SpanDev();
   int rc = p.decode_writables(static_cast<const uint8_t*>(buf), len, offs, n, &span);
@@ -755,23 +607,22 @@ int hbam_decode_writables(hbam_ctx* ctx, const void* buf, uint64_t len, const ui
 }
 
 int hbam_merge_begin(hbam_ctx* ctx, int32_t order) {
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
   if (ctx->merge) {
     ctx->err = "hbam_merge_begin: a merge is already open on this ctx (hbam_merge_end closes it)";
     return HBAM_E_STATE;
   }
-  if (order != HBAM_SORT_KEY && order != HBAM_SORT_COORDINATE && order != HBAM_SORT_QUERYNAME) {
+  if (!valid_sort_order(order)) {
     ctx->err = "unknown sort order " + std::to_string(order);
     return HBAM_E_ARG;
   }
-  hbam::Pipeline& p = ctx->f ? ctx->f->pipe() : *ctx->codec;
-  ctx->merge.reset(new hbam::Merger(p, order));
+  ctx->merge.reset(new hbam::Merger(*pipe_of(ctx), order));
   return HBAM_OK;
 }
 
 int hbam_merge_add_run(hbam_ctx* ctx, const uint8_t* buf, uint64_t len, const uint64_t* offs, uint64_t n,
                        const uint64_t* words) {
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
   if (!ctx->merge || ctx->merge->planned()) {
     ctx->err = ctx->merge ? "hbam_merge_add_run after hbam_merge_plan" : "hbam_merge_add_run needs hbam_merge_begin";
     return HBAM_E_STATE;
@@ -800,7 +651,7 @@ int hbam_merge_add_run(hbam_ctx* ctx, const uint8_t* buf, uint64_t len, const ui
 
 int hbam_merge_plan(hbam_ctx* ctx, uint64_t part_bytes, uint64_t* n_parts, uint64_t* n_records, uint64_t* bytes) {
   *n_parts = *n_records = *bytes = 0;
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
   if (!ctx->merge || ctx->merge->planned()) {
     ctx->err = ctx->merge ? "hbam_merge_plan was already called" : "hbam_merge_plan needs hbam_merge_begin";
     return HBAM_E_STATE;
@@ -813,7 +664,7 @@ int hbam_merge_plan(hbam_ctx* ctx, uint64_t part_bytes, uint64_t* n_parts, uint6
 int hbam_merge_next(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, uint64_t* src, uint64_t* n,
                     uint64_t* len) {
   *n = *len = 0;
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
   if (!ctx->merge || !ctx->merge->planned()) {
     ctx->err = "hbam_merge_next needs hbam_merge_plan";
     return HBAM_E_STATE;
@@ -824,16 +675,15 @@ int hbam_merge_next(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, u
 }
 
 int hbam_merge_end(hbam_ctx* ctx) {
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
   ctx->merge.reset();
   return HBAM_OK;
 }
 
 int hbam_sort_name_counters(hbam_ctx* ctx, uint64_t out[3]) {
   out[0] = out[1] = out[2] = 0;
-  if (!ctx || (!ctx->f && !ctx->codec)) return HBAM_E_STATE;
-  const hbam::Pipeline& p = ctx->f ? ctx->f->pipe() : *ctx->codec;
-  for (int i = 0; i < 3; ++i) out[i] = p.name_counters()[i];
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
+  sort_name_counters(*pipe_of(ctx), out);
   return HBAM_OK;
 }
 
@@ -857,11 +707,7 @@ int hbam_build_splitting_index(hbam_ctx* ctx, int32_t granularity, uint8_t** buf
     ctx->err = ctx->f->error();
     return rc;
   }
-  *buf = static_cast<uint8_t*>(malloc(out.size() ? out.size() : 1));
-  if (!*buf) return HBAM_E_NOMEM;
-  memcpy(*buf, out.data(), out.size());
-  *len = out.size();
-  return HBAM_OK;
+  return copy_out(out, buf, len);
 }
 
 int hbam_build_bai(hbam_ctx* ctx, int32_t flags, uint8_t** buf, uint64_t* len) {
@@ -877,11 +723,7 @@ int hbam_build_bai(hbam_ctx* ctx, int32_t flags, uint8_t** buf, uint64_t* len) {
   hadoop_bam::BaiBuilder b;
   const int rc = b.build(*ctx->f, (flags & HBAM_BAI_METADATA) != 0, &out, &ctx->err);
   if (rc != HBAM_OK) return rc;
-  *buf = static_cast<uint8_t*>(malloc(out.size() ? out.size() : 1));
-  if (!*buf) return HBAM_E_NOMEM;
-  memcpy(*buf, out.data(), out.size());
-  *len = out.size();
-  return HBAM_OK;
+  return copy_out(out, buf, len);
 }
 
 int hbam_bai_summarize(const void* bai, uint64_t len, hbam_bai_summary* out) {
@@ -907,11 +749,7 @@ int hbam_bai_query(const void* bai, uint64_t len, const hbam_interval* iv, uint6
   std::vector<uint64_t> out;
   rc = idx.query(reinterpret_cast<const hadoop_bam::QueryInterval*>(iv), n_iv, &out, &g_open_err);
   if (rc != HBAM_OK) return rc;
-  *file_pointers = static_cast<uint64_t*>(malloc(out.empty() ? 8 : out.size() * 8));
-  if (!*file_pointers) return HBAM_E_NOMEM;
-  if (!out.empty()) memcpy(*file_pointers, out.data(), out.size() * 8);
-  *n_ptrs = out.size();
-  return HBAM_OK;
+  return copy_out(out, file_pointers, n_ptrs);
 }
 
 int hbam_splitting_entries(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_t granularity, uint64_t ordinal0,
@@ -926,11 +764,7 @@ int hbam_splitting_entries(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_
     ctx->err = ctx->f->error();
     return rc;
   }
-  *entries = static_cast<uint64_t*>(malloc(ent.empty() ? 8 : ent.size() * 8));
-  if (!*entries) return HBAM_E_NOMEM;
-  if (!ent.empty()) memcpy(*entries, ent.data(), ent.size() * 8);
-  *n_entries = ent.size();
-  return HBAM_OK;
+  return copy_out(ent, entries, n_entries);
 }
 
 int hbam_splitting_index_for_records(const hbam_opts* opts, const uint64_t* voffs, uint64_t n, int32_t granularity,
@@ -943,10 +777,7 @@ int hbam_splitting_index_for_records(const hbam_opts* opts, const uint64_t* voff
   }
   hbam_opts o{};
   if (opts) o = *opts;
-  if (o.device < 0 || o.device >= hbam_device_count()) {
-    g_open_err = "no HIP device " + std::to_string(o.device);
-    return HBAM_E_DEVICE;
-  }
+  if (check_device(o.device) != HBAM_OK) return HBAM_E_DEVICE;
   // processAlignment (SplittingBAMIndexer.java:197-202): record 0, then every
   // record whose ordinal + 1 is a multiple of g; finish writes size << 16
   hbam::Pipeline p(o.device);
@@ -1089,406 +920,6 @@ int64_t hbam_get_key(int32_t ref_idx, int32_t alignment_start) {
 }
 int64_t hbam_murmurhash3(const void* key, uint64_t len, int32_t seed) {
   return hadoop_bam::murmurhash3(static_cast<const uint8_t*>(key), len, seed);
-}
-
-// ---- device-resident decode --------------------------------------------------
-int32_t hbam_device_count(void) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-int hbam_gpu_create(int32_t device, hbam_gpu** out) {
-  *out = nullptr;
-  int n = hbam_device_count();
-  if (device < 0 || device >= n) {
-    g_open_err = "no HIP device " + std::to_string(device);
-    return HBAM_E_DEVICE;
-  }
-  auto* g = new hbam_gpu();
-  g->device = device;
-  *out = g;
-  return HBAM_OK;
-}
-
-void hbam_gpu_destroy(hbam_gpu* g) { delete g; }
-
-const char* hbam_gpu_error(hbam_gpu* g) { return g ? g->err.c_str() : g_open_err.c_str(); }
-
-int hbam_gpu_load(hbam_gpu* g, const void* data, uint64_t len) {
-  OpenOptions o;
-  o.device = g->device;
-  o.window_bytes = g->window;
-  o.stringency = g->stringency;
-  g->enc.release();  // owned by the old file's pipeline streams
-  g->enc.owner = nullptr;
-  g->f.reset();
-  g->span = hbam::SpanDev();
-  std::string err;
-  int rc = BamFile::open_device_copy(static_cast<const uint8_t*>(data), len, o, &g->f, &err);
-  if (rc != HBAM_OK) g->err = err;
-  return rc;
-}
-
-int hbam_gpu_set_window(hbam_gpu* g, uint64_t window_bytes) {
-  g->window = window_bytes ? window_bytes : hadoop_bam::kDefaultWindowBytes;
-  if (g->f) g->f->set_window_bytes(g->window);
-  return HBAM_OK;
-}
-
-int hbam_gpu_set_stringency(hbam_gpu* g, int32_t stringency) {
-  if (stringency < HBAM_STRICT || stringency > HBAM_SILENT) {
-    g->err = "unknown validation stringency";
-    return HBAM_E_ARG;
-  }
-  g->stringency = stringency;
-  return HBAM_OK;
-}
-
-int hbam_gpu_set_locate(hbam_gpu* g, uint64_t seg_bytes, uint32_t cap_limit) {
-  if (!g->f) {
-    g->err = "hbam_gpu_set_locate needs a loaded file";
-    return HBAM_E_STATE;
-  }
-  set_locate(*g->f, seg_bytes, cap_limit);
-  return HBAM_OK;
-}
-
-int hbam_gpu_locate_counters(hbam_gpu* g, uint64_t out[2]) {
-  out[0] = out[1] = 0;
-  if (!g->f) return HBAM_E_STATE;
-  out[0] = g->f->pipe().locate_anchored();
-  out[1] = g->f->pipe().locate_declined();
-  return HBAM_OK;
-}
-
-int hbam_gpu_run(hbam_gpu* g, int32_t flags, hbam_gpu_stats* st) {
-  memset(st, 0, sizeof *st);
-  if (!g->f) {
-    g->err = "hbam_gpu_run needs a loaded file";
-    return HBAM_E_STATE;
-  }
-  return decode_device(*g->f, g->f->first_record_voff(), ~0ull, flags, st, &g->span, &g->err);
-}
-
-int hbam_gpu_index(hbam_gpu* g, int32_t granularity, uint8_t** buf, uint64_t* len, float* ms) {
-  *buf = nullptr;
-  *len = 0;
-  *ms = 0;
-  if (!g->f) return HBAM_E_STATE;
-  hbam::Pipeline& p = g->f->pipe();
-  p.timing = false;
-  g->f->invalidate_window();
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, p.stream());
-  std::vector<uint8_t> out;
-  int rc = SplittingBAMIndexer::index(*g->f, granularity, &out);
-  (void)hipEventRecord(e1, p.stream());
-  (void)hipEventSynchronize(e1);
-  (void)hipEventElapsedTime(ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  g->span = hbam::SpanDev();
-  if (rc != HBAM_OK) {
-    g->err = g->f->error();
-    return rc;
-  }
-  *buf = static_cast<uint8_t*>(malloc(out.size() ? out.size() : 1));
-  if (!*buf) return HBAM_E_NOMEM;
-  memcpy(*buf, out.data(), out.size());
-  *len = out.size();
-  return HBAM_OK;
-}
-
-int hbam_gpu_run_streamed(hbam_gpu* g, const void* data, uint64_t len, uint64_t piece_bytes, hbam_gpu_stats* st) {
-  memset(st, 0, sizeof *st);
-  if (!g->f || len != g->f->file_size()) {
-    g->err = "hbam_gpu_run_streamed needs the loaded file's bytes";
-    return HBAM_E_STATE;
-  }
-  hbam::Pipeline& p = g->f->pipe();
-  p.timing = false;
-  g->f->invalidate_window();
-  // one window holding the whole file in the pipeline's own buffer (untimed)
-  int rc = p.load(static_cast<const uint8_t*>(data), len, 0, true);
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    return rc;
-  }
-  const uint64_t il0 = p.inflate_launches();
-  g->span = hbam::SpanDev();
-  // first record: the header end (the same position the resident pass starts at)
-  std::unique_ptr<BamFile>& f = g->f;
-  rc = p.locate();
-  uint64_t first_pos = 0;
-  if (rc == HBAM_OK) {
-    const int64_t fp = p.pos_of_voff(f->first_record_voff());
-    if (fp < 0) rc = HBAM_E_STATE;
-    first_pos = (uint64_t)std::max<int64_t>(fp, 0);
-  }
-  if (rc == HBAM_OK)
-    rc = p.run_streamed(static_cast<const uint8_t*>(data), len, piece_bytes, first_pos, &g->span, &st->ms_total);
-  g->f->invalidate_window();
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    st->status = rc;
-    return rc;
-  }
-  st->n_blocks = p.blocks().size();
-  st->compressed_bytes = p.file_len();
-  st->inflated_bytes = p.total_u();
-  st->records = g->span.n;
-  st->status = g->span.status;
-  st->windows = 1;
-  st->inflate_launches = (int32_t)(p.inflate_launches() - il0);
-  if (g->span.n) {
-    (void)hipMemcpy(&st->first_voff, g->span.rec_voff, 8, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&st->last_voff, g->span.rec_voff + g->span.n - 1, 8, hipMemcpyDeviceToHost);
-  }
-  if (g->span.status != HBAM_OK) g->err = g->span.error;
-  return g->span.status;
-}
-
-void* hbam_host_alloc(uint64_t bytes) {
-  // the library's page-locked blocks: on the current device's NUMA node (hbam_mem.cpp)
-  void* p = nullptr;
-  size_t got = 0;
-  if (hbam::pinned_alloc(&p, bytes ? bytes : 1, &got) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(host_alloc_mu());
-  host_allocs()[p] = got;
-  return p;
-}
-
-void hbam_host_free(void* p) {
-  if (!p) return;
-  size_t bytes = 0;
-  {
-    std::lock_guard<std::mutex> lk(host_alloc_mu());
-    auto it = host_allocs().find(p);
-    if (it == host_allocs().end()) return;
-    bytes = it->second;
-    host_allocs().erase(it);
-  }
-  hbam::pinned_free(p, bytes);
-}
-
-int hbam_gpu_reload(hbam_gpu* g, const void* data, uint64_t len, int32_t pinned, float* ms) {
-  *ms = 0;
-  if (!g->f) return HBAM_E_STATE;
-  hbam::Pipeline& p = g->f->pipe();
-  g->f->invalidate_window();
-  int rc = p.load(static_cast<const uint8_t*>(data), len, 0, true);  // the copy target (untimed)
-  if (rc == HBAM_OK) rc = p.reload(static_cast<const uint8_t*>(data), len, pinned != 0, ms);
-  if (rc != HBAM_OK) g->err = p.error();
-  g->span = hbam::SpanDev();
-  return rc;
-}
-
-int hbam_gpu_d2d_bandwidth(hbam_gpu* g, uint64_t bytes, int32_t iters, float* gbps) {
-  if (!g->f) return HBAM_E_STATE;
-  int rc = g->f->pipe().d2d_bandwidth(bytes, iters, gbps);
-  if (rc != HBAM_OK) g->err = g->f->pipe().error();
-  return rc;
-}
-
-int hbam_gpu_encode_writables(hbam_gpu* g, int32_t iters, float* ms_per_iter, uint64_t* bytes) {
-  *ms_per_iter = 0;
-  *bytes = 0;
-  if (!g->f) return HBAM_E_STATE;
-  hbam::Pipeline& p = g->f->pipe();
-  uint64_t nb = 0;
-  g->enc.owner = &p.streams();
-  int rc = p.encoded_bytes(g->span, &nb);
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    return rc;
-  }
-  if (g->enc.reserve((nb + 15) & ~15ull) != hipSuccess) {
-    g->err = "hipMalloc failed";
-    return HBAM_E_DEVICE;
-  }
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  rc = p.encode_writables(g->span, nb, g->enc.p);  // warm-up (also checks the launch)
-  if (rc == HBAM_OK) {
-    (void)hipEventRecord(e0, p.stream());
-    for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) rc = p.encode_writables(g->span, nb, g->enc.p);
-    (void)hipEventRecord(e1, p.stream());
-    (void)hipEventSynchronize(e1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *ms_per_iter = iters > 0 ? ms / (float)iters : 0.f;
-  }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    return rc;
-  }
-  g->enc_bytes = nb;
-  *bytes = nb;
-  return HBAM_OK;
-}
-
-int hbam_gpu_sort_writables(hbam_gpu* g, int32_t order, int32_t iters, float ms[3], uint64_t* bytes) {
-  ms[0] = ms[1] = ms[2] = 0;
-  *bytes = 0;
-  if (!g->f) return HBAM_E_STATE;
-  hbam::Pipeline& p = g->f->pipe();
-  uint64_t nb = 0;
-  g->enc.owner = &p.streams();
-  int rc = p.encoded_bytes(g->span, &nb);
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    return rc;
-  }
-  if (g->enc.reserve((nb + 15) & ~15ull) != hipSuccess) {
-    g->err = "hipMalloc failed";
-    return HBAM_E_DEVICE;
-  }
-  rc = p.sort_writables(g->span, order, nb, g->enc.p);  // warm-up (also checks the launches)
-  for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) {
-    float t[3];
-    rc = p.sort_writables(g->span, order, nb, g->enc.p, t);
-    for (int k = 0; k < 3; ++k) ms[k] += t[k] / (float)iters;
-  }
-  if (rc == HBAM_OK && hipStreamSynchronize(p.stream()) != hipSuccess) {
-    g->err = "hipStreamSynchronize failed";
-    return HBAM_E_DEVICE;
-  }
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    return rc;
-  }
-  g->enc_bytes = nb;
-  *bytes = nb;
-  return HBAM_OK;
-}
-
-int hbam_gpu_format_sam(hbam_gpu* g, int32_t iters, float ms[3], uint64_t* bytes) {
-  ms[0] = ms[1] = ms[2] = 0;
-  *bytes = 0;
-  if (!g->f) return HBAM_E_STATE;
-  hbam::Pipeline& p = g->f->pipe();
-  g->enc.owner = &p.streams();
-  uint64_t nb = 0, bad = ~0ull;
-  int rc = p.set_sam_refs(g->f->ref_names());
-  if (rc == HBAM_OK) rc = p.sam_measure(g->span, &nb, &bad);  // warm-up: sizes the text
-  if (rc == HBAM_OK && bad != ~0ull) {
-    g->err = "malformed aux fields in record " + std::to_string(bad) + " of the window";
-    return HBAM_E_FORMAT;
-  }
-  if (rc == HBAM_OK && g->enc.reserve((nb + 15) & ~15ull) != hipSuccess) {
-    g->err = "device allocation of the SAM text failed";
-    return HBAM_E_NOMEM;
-  }
-  if (rc == HBAM_OK) rc = p.sam_write(g->span, nb, g->enc.p);
-  for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) {
-    float t[3] = {0, 0, 0};
-    rc = p.sam_measure(g->span, &nb, &bad, t);
-    if (rc == HBAM_OK) rc = p.sam_write(g->span, nb, g->enc.p, t + 2);
-    for (int k = 0; k < 3; ++k) ms[k] += t[k] / (float)iters;
-  }
-  if (rc == HBAM_OK && hipStreamSynchronize(p.stream()) != hipSuccess) {
-    g->err = "hipStreamSynchronize failed";
-    return HBAM_E_DEVICE;
-  }
-  if (rc != HBAM_OK) {
-    g->err = p.error();
-    return rc;
-  }
-  g->enc_bytes = nb;
-  *bytes = nb;
-  return HBAM_OK;
-}
-
-int hbam_gpu_sort_name_counters(hbam_gpu* g, uint64_t out[3]) {
-  out[0] = out[1] = out[2] = 0;
-  if (!g->f) return HBAM_E_STATE;
-  for (int i = 0; i < 3; ++i) out[i] = g->f->pipe().name_counters()[i];
-  return HBAM_OK;
-}
-
-int hbam_gpu_sort_name_times(hbam_gpu* g, float ms[3]) {
-  ms[0] = ms[1] = ms[2] = 0;
-  if (!g->f) return HBAM_E_STATE;
-  for (int i = 0; i < 3; ++i) ms[i] = g->f->pipe().name_times()[i];
-  return HBAM_OK;
-}
-
-int hbam_gpu_fetch_encoded(hbam_gpu* g, uint64_t pos, uint64_t len, uint8_t* dst) {
-  if (pos > g->enc_bytes || len > g->enc_bytes - pos) {
-    g->err = "range outside the encoded records";
-    return HBAM_E_ARG;
-  }
-  if (len && hipMemcpy(dst, g->enc.p + pos, len, hipMemcpyDeviceToHost) != hipSuccess) return HBAM_E_DEVICE;
-  return HBAM_OK;
-}
-
-int hbam_gpu_bgzf_compress(hbam_gpu* g, int32_t level, int32_t flags, int32_t iters, float* ms_per_iter,
-                           uint64_t* out_len) {
-  *ms_per_iter = 0;
-  *out_len = 0;
-  if (!g->f) return HBAM_E_STATE;
-  hbam::Pipeline& p = g->f->pipe();
-  if (!p.d_u() || p.base() != 0 || !p.at_eof() || p.blocks().empty()) {
-    g->err = "hbam_gpu_bgzf_compress needs a one-window run (inflated stream) first";
-    return HBAM_E_STATE;
-  }
-  std::vector<uint64_t> ustart;
-  std::vector<uint32_t> lens;
-  const auto& B = p.blocks();
-  // the input's EOF terminator is re-added by HBAM_BGZF_EOF, not recompressed
-  size_t nb = B.size();
-  if ((flags & HBAM_BGZF_EOF) && nb && B[nb - 1].isize == 0) --nb;
-  for (size_t i = 0; i < nb; ++i) {
-    ustart.push_back(B[i].ustart);
-    lens.push_back(B[i].isize);
-  }
-  // the run inflated the blocks from the first record on; the header's too
-  int rc0 = p.inflate(0, (uint32_t)B.size());
-  if (rc0 != HBAM_OK) {
-    g->err = p.error();
-    return rc0;
-  }
-  if (!g->bgzf) g->bgzf.reset(new hbam::BgzfCompressor(p.device()));
-  float ms = 0, tot = 0;
-  int rc = g->bgzf->compress(p.d_u(), ustart, lens, level, (flags & HBAM_BGZF_EOF) != 0, p.stream(), &ms);
-  for (int32_t i = 0; i < iters && rc == HBAM_OK; ++i) {
-    rc = g->bgzf->compress(p.d_u(), ustart, lens, level, (flags & HBAM_BGZF_EOF) != 0, p.stream(), &ms);
-    tot += ms;
-  }
-  if (rc != HBAM_OK) {
-    g->err = g->bgzf->error();
-    return rc;
-  }
-  *ms_per_iter = iters > 0 ? tot / (float)iters : ms;
-  *out_len = g->bgzf->out_len();
-  return HBAM_OK;
-}
-
-int hbam_gpu_fetch_compressed(hbam_gpu* g, uint64_t pos, uint64_t len, uint8_t* dst) {
-  const uint64_t n = g->bgzf ? g->bgzf->out_len() : 0;
-  if (pos > n || len > n - pos) {
-    g->err = "range outside the compressed output";
-    return HBAM_E_ARG;
-  }
-  if (len && hipMemcpy(dst, g->bgzf->d_out() + pos, len, hipMemcpyDeviceToHost) != hipSuccess) return HBAM_E_DEVICE;
-  return HBAM_OK;
-}
-
-int hbam_gpu_fetch(hbam_gpu* g, int64_t* keys, uint64_t* voffs, uint64_t cap) {
-  const uint64_t n = std::min<uint64_t>(cap, g->span.n);
-  if (keys && n && g->span.col.key) {
-    if (hipMemcpy(keys, g->span.col.key, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return HBAM_E_DEVICE;
-  }
-  if (voffs && n) {
-    if (hipMemcpy(voffs, g->span.rec_voff, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return HBAM_E_DEVICE;
-  }
-  return HBAM_OK;
 }
 
 }  // extern "C"

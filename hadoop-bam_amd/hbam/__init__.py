@@ -337,13 +337,17 @@ class _Merge:
     BamFile).  The runs' bytes stay in host memory; the order is planned and
     every part gathered on the GPU."""
 
-    def _merge_err(self, rc):
+    def _err(self, rc):
         return HbamError(rc, _L.hbam_last_error(self._h).decode(errors="replace"))
+
+    def _ok(self, rc):
+        """Raise the ctx's error unless rc is OK (BamFile and Codec share it)."""
+        if rc != OK:
+            raise self._err(rc)
 
     def merge_begin(self, order="key"):
         rc = _L.hbam_merge_begin(self._h, SORT_ORDERS.get(order, order))
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         self._merge_keep = []
 
     def merge_add_run(self, enc, offs, words=None):
@@ -366,16 +370,14 @@ class _Merge:
         keep = (enc, buf, o, w)
         rc = _L.hbam_merge_add_run(self._h, buf.ctypes.data if len(buf) else None, len(buf), o.ctypes.data,
                                    len(o) - 1, w.ctypes.data if w is not None and len(w) else None)
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         self._merge_keep.append(keep)
 
     def merge_plan(self, part_bytes=0):
         """(parts, records, bytes) of the merged output, cut every part_bytes (0: 1 GiB)."""
         a, b, c = u64(), u64(), u64()
         rc = _L.hbam_merge_plan(self._h, part_bytes, C.byref(a), C.byref(b), C.byref(c))
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         return a.value, b.value, c.value
 
     def merge_next(self):
@@ -383,16 +385,14 @@ class _Merge:
         src[u64, n] = run << 32 | record index in that run); None after the last."""
         n, ln = u64(), u64()
         rc = _L.hbam_merge_next(self._h, None, 0, None, None, C.byref(n), C.byref(ln))
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         if n.value == 0:
             return None
         out = C.create_string_buffer(max(ln.value, 1))
         offs = np.zeros(n.value + 1, np.uint64)
         src = np.zeros(n.value, np.uint64)
         rc = _L.hbam_merge_next(self._h, out, ln.value, offs.ctypes.data, src.ctypes.data, C.byref(n), C.byref(ln))
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         return out.raw[:ln.value], offs, src
 
     def sort_name_counters(self):
@@ -401,8 +401,7 @@ class _Merge:
         (hbam_sort_name_counters)."""
         w = (u64 * 3)()
         rc = _L.hbam_sort_name_counters(self._h, w)
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         return int(w[0]), int(w[1]), int(w[2])
 
     def merge_end(self):
@@ -414,8 +413,7 @@ class _Merge:
         """(plan_ms[3], part_ms[3]) of the open merge (hbam_merge_times)."""
         a, b = (C.c_float * 3)(), (C.c_float * 3)()
         rc = _L.hbam_merge_times(self._h, a, b)
-        if rc != OK:
-            raise self._merge_err(rc)
+        self._ok(rc)
         return list(a), list(b)
 
     def iter_merged(self, part_bytes=0):
@@ -528,14 +526,10 @@ class BamFile(_Merge):
         except Exception:
             pass
 
-    def _err(self, rc):
-        return HbamError(rc, _L.hbam_last_error(self._h).decode(errors="replace"))
-
     def header(self):
         h = HeaderInfo()
         rc = _L.hbam_header(self._h, C.byref(h))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         text = C.string_at(h.text, h.l_text).decode(errors="replace") if h.l_text else ""
         return {"n_ref": h.n_ref, "l_text": h.l_text, "first_record_voff": h.first_record_voff,
                 "file_size": h.file_size, "text": text}
@@ -545,16 +539,14 @@ class BamFile(_Merge):
         the references), rebuilt from hbam_header and hbam_ref."""
         h = HeaderInfo()
         rc = _L.hbam_header(self._h, C.byref(h))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         text = C.string_at(h.text, h.l_text) if h.l_text else b""
         out = [b"BAM\x01", len(text).to_bytes(4, "little"), text, h.n_ref.to_bytes(4, "little")]
         for i in range(h.n_ref):
             name = C.c_char_p()
             ln = i32()
             rc = _L.hbam_ref(self._h, i, C.byref(name), C.byref(ln))
-            if rc != OK:
-                raise self._err(rc)
+            self._ok(rc)
             out += [(len(name.value) + 1).to_bytes(4, "little"), name.value, b"\0",
                     ln.value.to_bytes(4, "little", signed=True)]
         return b"".join(out)
@@ -563,41 +555,35 @@ class BamFile(_Merge):
         """(BGZF blocks, inflated bytes) of the whole file."""
         nb, us = u64(), u64()
         rc = _L.hbam_file_stats(self._h, C.byref(nb), C.byref(us))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return nb.value, us.value
 
     def bytes_read(self):
         """Host -> HBM bytes this file has copied so far."""
         n = u64()
         rc = _L.hbam_bytes_read(self._h, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return n.value
 
     def prefetch(self, lo, hi):
         rc = _L.hbam_prefetch(self._h, lo, hi)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
 
     def reader_position(self, i):
         """BAMRecordReader.getProgress's in.position() after record i of the last batch."""
         v = u64()
         rc = _L.hbam_reader_position(self._h, i, C.byref(v))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return v.value
 
     def pipeline_counters(self):
         """Cumulative path counters of the ctx (hbam_pipeline_counters)."""
         v = (u64 * 5)()
         rc = _L.hbam_pipeline_counters(self._h, v)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         w = (u64 * 2)()
         rc = _L.hbam_locate_counters(self._h, w)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return dict(zip(("link_fallbacks", "link_rewalks", "record_fallbacks", "inflate_launches",
                          "records_after_stop", "locate_anchored", "locate_declined"),
                         (int(x) for x in list(v) + list(w))))
@@ -606,16 +592,14 @@ class BamFile(_Merge):
         """hbam_set_locate: the anchored locate's segment bytes (0: the full
         scan only) and a bound on a range's candidate capacity (0: none)."""
         rc = _L.hbam_set_locate(self._h, seg_bytes, cap_limit)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
 
     def inflate_token_count(self):
         """LZ77 tokens phase A wrote in the last pass over the current window
         (hbam_inflate_token_count)."""
         v = u64()
         rc = _L.hbam_inflate_token_count(self._h, C.byref(v))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return int(v.value)
 
     def inflate_path_counts(self):
@@ -624,8 +608,7 @@ class BamFile(_Merge):
         the lean kernel's resident workgroups per CU (hbam_inflate_path_counts)."""
         v = (u64 * 3)()
         rc = _L.hbam_inflate_path_counts(self._h, v)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return int(v[0]), int(v[1]), int(v[2])
 
     def inflate_narrow_counts(self):
@@ -635,8 +618,7 @@ class BamFile(_Merge):
         bytes of window its stage holds (hbam_inflate_narrow_counts)."""
         v = (u64 * 3)()
         rc = _L.hbam_inflate_narrow_counts(self._h, v)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return int(v[0]), int(v[1]), int(v[2])
 
     def chain_counters(self):
@@ -646,8 +628,7 @@ class BamFile(_Merge):
         rounds."""
         v = (u64 * 4)()
         rc = _L.hbam_chain_counters(self._h, v)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return dict(zip(("searched", "rewalked", "dropped", "link_rounds"), (int(x) for x in v)))
 
     def decode_span_device(self, vstart, vend, timing=False, decode=True, digest=True):
@@ -655,16 +636,14 @@ class BamFile(_Merge):
         st = GpuStats()
         flags = (1 if timing else 0) | (0 if decode else 2) | (4 if digest else 0)
         rc = _L.hbam_decode_span_device(self._h, vstart, vend, flags, C.byref(st))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return _stats_dict(st)
 
     def ref(self, i):
         name = C.c_char_p()
         ln = i32()
         rc = _L.hbam_ref(self._h, i, C.byref(name), C.byref(ln))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return name.value.decode(), ln.value
 
     def decode_span(self, vstart, vend, raise_on_error=True, max_records=0):
@@ -699,8 +678,7 @@ class BamFile(_Merge):
         v, n, k, nbytes = vstart, 0, 0, 0
         while v < vend:
             rc = _L.hbam_decode_span(self._h, v, vend, max_records, C.byref(b))
-            if rc != OK:
-                raise self._err(rc)
+            self._ok(rc)
             if b.n == 0:
                 break
             n += b.n
@@ -718,14 +696,12 @@ class BamFile(_Merge):
         fp = np.ascontiguousarray(file_pointers, np.uint64)
         rc = _L.hbam_query_intervals(self._h, iv.ctypes.data if len(iv) else None, len(iv),
                                      fp.ctypes.data if len(fp) else None, len(fp))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
 
     def query_unmapped(self, start_voff):
         """Open the unmapped-only query (hbam_query_unmapped) reading from start_voff."""
         rc = _L.hbam_query_unmapped(self._h, start_voff)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
 
     def query_next(self, max_records=0, raise_on_error=True):
         """The next records of the open query (at most max_records; 0 = all
@@ -745,8 +721,7 @@ class BamFile(_Merge):
         n, k, nbytes = 0, 0, 0
         while True:
             rc = _L.hbam_query_next(self._h, max_records, C.byref(b))
-            if rc != OK:
-                raise self._err(rc)
+            self._ok(rc)
             if b.n == 0:
                 break
             n += b.n
@@ -764,14 +739,12 @@ class BamFile(_Merge):
         (GPU): (bytes, offsets[n+1])."""
         n = u64()
         rc = _L.hbam_encode_writables(self._h, None, 0, None, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         total = n.value
         out = C.create_string_buffer(max(total, 1))
         offs = np.zeros(self._last_n + 1, np.uint64)
         rc = _L.hbam_encode_writables(self._h, out, total, offs.ctypes.data, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return out.raw[:total], offs
 
     def sort_writables(self, order="key"):
@@ -785,16 +758,14 @@ class BamFile(_Merge):
         o = SORT_ORDERS.get(order, order)
         n = u64()
         rc = _L.hbam_sort_writables(self._h, o, None, 0, None, None, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         total = n.value
         out = C.create_string_buffer(max(total, 1))
         offs = np.zeros(self._last_n + 1, np.uint64)
         perm = np.zeros(self._last_n, np.uint32)
         rc = _L.hbam_sort_writables(self._h, o, out, total, offs.ctypes.data,
                                     perm.ctypes.data if self._last_n else None, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return out.raw[:total], offs, perm
 
     def format_sam(self):
@@ -804,13 +775,11 @@ class BamFile(_Merge):
         n = u64()
         offs = np.zeros(self._last_n + 1, np.uint64)
         rc = _L.hbam_format_sam(self._h, None, 0, offs.ctypes.data, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         total = n.value
         out = C.create_string_buffer(max(total, 1))
         rc = _L.hbam_format_sam(self._h, out, total, offs.ctypes.data, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return out.raw[:total], offs
 
     def decode_writables(self, buf: bytes, offs, raise_on_error=True):
@@ -823,8 +792,7 @@ class BamFile(_Merge):
         p = P()
         n = u64()
         rc = _L.hbam_build_splitting_index(self._h, granularity, C.byref(p), C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         b = C.string_at(p, n.value)
         _L.hbam_free(p)
         return b
@@ -835,8 +803,7 @@ class BamFile(_Merge):
         p = P()
         n = u64()
         rc = _L.hbam_build_bai(self._h, BAI_METADATA if metadata else 0, C.byref(p), C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         try:
             return C.string_at(p, n.value)
         finally:
@@ -850,8 +817,7 @@ class BamFile(_Merge):
         nr = u64()
         rc = _L.hbam_splitting_entries(self._h, vstart, vend, granularity, ordinal0, C.byref(p), C.byref(ne),
                                        C.byref(nr))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         try:
             ent = np.frombuffer(C.string_at(p, 8 * ne.value), np.uint64).copy() if ne.value else np.zeros(0, np.uint64)
         finally:
@@ -871,8 +837,7 @@ class BamFile(_Merge):
         else:
             rc = _L.hbam_guess_record_starts_hdr(self._h, int(header_n_ref), b.ctypes.data, e.ctypes.data, n,
                                                  out.ctypes.data)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return [int(x) for x in out[:n]]
 
     def guess_bgzf_block_starts(self, begs, ends):
@@ -882,8 +847,7 @@ class BamFile(_Merge):
         e = np.ascontiguousarray(ends, np.uint64)
         out = np.zeros(max(n, 1), np.uint64)
         rc = _L.hbam_guess_bgzf_block_starts(self._h, b.ctypes.data, e.ctypes.data, n, out.ctypes.data)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return [int(x) for x in out[:n]]
 
     def get_splits(self, starts, lengths, sbi: bytes = None, bai: bytes = None):
@@ -902,8 +866,7 @@ class BamFile(_Merge):
         rc = _L.hbam_get_splits_bai(self._h, s.ctypes.data, ln.ctypes.data, n, sb,
                                     len(sbi) if sbi is not None else 0, bb, len(bai) if bai is not None else 0,
                                     vs.ctypes.data, ve.ctypes.data, C.byref(nout))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return [(int(vs[i]), int(ve[i])) for i in range(nout.value)]
 
     def blocks(self):
@@ -916,15 +879,13 @@ class BamFile(_Merge):
         ustart = np.zeros(max(k, 1), np.uint64)
         rc = _L.hbam_blocks(self._h, coff.ctypes.data, csize.ctypes.data, isize.ctypes.data,
                             ustart.ctypes.data, k, C.byref(n))
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return {"coff": coff[:k], "csize": csize[:k], "isize": isize[:k], "ustart": ustart[:k]}
 
     def read_inflated(self, pos, length):
         buf = C.create_string_buffer(max(length, 1))
         rc = _L.hbam_read_inflated(self._h, pos, length, buf)
-        if rc != OK:
-            raise self._err(rc)
+        self._ok(rc)
         return buf.raw[:length]
 
 
@@ -1009,6 +970,10 @@ class Gpu:
         except Exception:
             pass
 
+    def _ok(self, rc):
+        if rc != OK:
+            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+
     def load(self, data):
         """Make a whole BAM resident in HBM (header parsed)."""
         if isinstance(data, np.ndarray):
@@ -1018,8 +983,7 @@ class Gpu:
             self._keep = C.create_string_buffer(bytes(data), len(data))
             ptr, n = self._keep, len(data)
         rc = _L.hbam_gpu_load(self._h, ptr, n)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         self._keep = None
 
     def set_window(self, window_bytes):
@@ -1028,29 +992,25 @@ class Gpu:
     def set_stringency(self, stringency):
         """Validation stringency of the files loaded from now on (default STRICT)."""
         rc = _L.hbam_gpu_set_stringency(self._h, stringency)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
 
     def set_locate(self, seg_bytes=LOCATE_SEG_DEFAULT, cap_limit=0):
         """hbam_gpu_set_locate (see BamFile.set_locate); needs a loaded file."""
         rc = _L.hbam_gpu_set_locate(self._h, seg_bytes, cap_limit)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
 
     def locate_counters(self):
         """(locate_anchored, locate_declined) of the loaded file's pipeline."""
         w = (u64 * 2)()
         rc = _L.hbam_gpu_locate_counters(self._h, w)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return int(w[0]), int(w[1])
 
     def run(self, timing=False, decode=True, digest=False):
         st = GpuStats()
         flags = (1 if timing else 0) | (0 if decode else 2) | (4 if digest else 0)
         rc = _L.hbam_gpu_run(self._h, flags, C.byref(st))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return _stats_dict(st)
 
     def index(self, granularity=4096):
@@ -1059,8 +1019,7 @@ class Gpu:
         n = u64()
         ms = C.c_float()
         rc = _L.hbam_gpu_index(self._h, granularity, C.byref(p), C.byref(n), C.byref(ms))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         b = C.string_at(p, n.value)
         _L.hbam_free(p)
         return b, ms.value
@@ -1070,8 +1029,7 @@ class Gpu:
         pieces while inflating the pieces already in HBM, then chain + decode."""
         st = GpuStats()
         rc = _L.hbam_gpu_run_streamed(self._h, ptr, nbytes, piece_bytes, C.byref(st))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return _stats_dict(st)
 
     def reload(self, ptr, nbytes, pinned=True):
@@ -1079,15 +1037,13 @@ class Gpu:
         page-locked staging copy if pinned), timed: milliseconds."""
         ms = C.c_float()
         rc = _L.hbam_gpu_reload(self._h, ptr, nbytes, int(pinned), C.byref(ms))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return ms.value
 
     def d2d_bandwidth(self, nbytes=1 << 32, iters=5):
         gbps = C.c_float()
         rc = _L.hbam_gpu_d2d_bandwidth(self._h, nbytes, iters, C.byref(gbps))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return gbps.value
 
     def encode_writables(self, iters=10):
@@ -1096,8 +1052,7 @@ class Gpu:
         ms = C.c_float()
         nb = u64()
         rc = _L.hbam_gpu_encode_writables(self._h, iters, C.byref(ms), C.byref(nb))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return ms.value, nb.value
 
     def sort_writables(self, order="key", iters=10):
@@ -1107,8 +1062,7 @@ class Gpu:
         ms = (C.c_float * 3)()
         nb = u64()
         rc = _L.hbam_gpu_sort_writables(self._h, SORT_ORDERS.get(order, order), iters, ms, C.byref(nb))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return (ms[0], ms[1], ms[2]), nb.value
 
     def format_sam(self, iters=10):
@@ -1118,8 +1072,7 @@ class Gpu:
         ms = (C.c_float * 3)()
         nb = u64()
         rc = _L.hbam_gpu_format_sam(self._h, iters, ms, C.byref(nb))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return (ms[0], ms[1], ms[2]), nb.value
 
     def sort_name_counters(self):
@@ -1127,8 +1080,7 @@ class Gpu:
         queryname sort_writables (hbam_gpu_sort_name_counters)."""
         w = (u64 * 3)()
         rc = _L.hbam_gpu_sort_name_counters(self._h, w)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return int(w[0]), int(w[1]), int(w[2])
 
     def sort_name_times(self):
@@ -1137,15 +1089,13 @@ class Gpu:
         sort_writables (hbam_gpu_sort_name_times)."""
         ms = (C.c_float * 3)()
         rc = _L.hbam_gpu_sort_name_times(self._h, ms)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return ms[0], ms[1], ms[2]
 
     def fetch_encoded(self, pos, length):
         buf = C.create_string_buffer(max(length, 1))
         rc = _L.hbam_gpu_fetch_encoded(self._h, pos, length, buf)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return buf.raw[:length]
 
     def bgzf_compress(self, level=5, eof=True, iters=0):
@@ -1154,15 +1104,13 @@ class Gpu:
         ms = C.c_float()
         nb = u64()
         rc = _L.hbam_gpu_bgzf_compress(self._h, level, BGZF_EOF if eof else 0, iters, C.byref(ms), C.byref(nb))
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return ms.value, nb.value
 
     def fetch_compressed(self, pos, length):
         buf = np.empty(max(length, 1), np.uint8)
         rc = _L.hbam_gpu_fetch_compressed(self._h, pos, length, buf.ctypes.data)
-        if rc != OK:
-            raise HbamError(rc, _L.hbam_gpu_error(self._h).decode())
+        self._ok(rc)
         return buf[:length]
 
     def fetch(self, n):
