@@ -45,6 +45,9 @@ struct hbam_ctx {
   hadoop_bam::BatchView batch;  // the last batch handed out (cursor slots or wbatch)
   hbam::SpanDev wspan;  // device result of the last hbam_decode_writables
   LastBatch last = LastBatch::kNone;
+  // hbam_parse_sam's dictionary on the pipeline: none uploaded yet (the next parse uploads the file's, or an
+  // empty one on a codec ctx), the file's, or the caller's (hbam_parse_sam_dict)
+  enum class SamDict { kUnset, kFile, kCaller } sam_dict = SamDict::kUnset;
   std::unique_ptr<QueryCursor> query;  // the open bounded traversal (hbam_query_*), if any
   std::unique_ptr<hbam::Merger> merge;  // the open merge (hbam_merge_*), if any (destroyed first: its buffers
                                         // wait for the pipeline's streams)
@@ -536,6 +539,134 @@ int hbam_format_sam(hbam_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* offs, u
   if ((rc = check_cap(ctx, cap, bytes, "SAM text")) != HBAM_OK) return rc;
   return write_and_copy_back(ctx, p, out, bytes, "device allocation of the SAM text failed", HBAM_E_NOMEM,
                              [&](uint8_t* dst, D2H*) { return p.sam_write(span, bytes, dst); });
+}
+
+int hbam_parse_sam_dict(hbam_ctx* ctx, const char* const* names, int32_t n_ref) {
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
+  if (!names && n_ref == -1) {  // back to the file's own (uploaded by the next parse)
+    ctx->sam_dict = hbam_ctx::SamDict::kUnset;
+    return HBAM_OK;
+  }
+  if (n_ref < 0 || (n_ref > 0 && !names)) {
+    ctx->err = "hbam_parse_sam_dict: n_ref names, or NULL and -1";
+    return HBAM_E_ARG;
+  }
+  std::vector<std::string> v;
+  for (int32_t i = 0; i < n_ref; ++i) {
+    if (!names[i]) {
+      ctx->err = "hbam_parse_sam_dict: name " + std::to_string(i) + " is NULL";
+      return HBAM_E_ARG;
+    }
+    v.emplace_back(names[i]);
+  }
+  hbam::Pipeline& p = *pipe_of(ctx);
+  ctx->sam_dict = hbam_ctx::SamDict::kUnset;
+  const int rc = p.samp_set_dict(v);
+  if (rc != HBAM_OK) {
+    ctx->err = p.error();
+    return rc;
+  }
+  ctx->sam_dict = hbam_ctx::SamDict::kCaller;
+  return HBAM_OK;
+}
+
+int hbam_parse_sam(hbam_ctx* ctx, const void* text, uint64_t len, int32_t final, hbam_sam_records* out) {
+  memset(out, 0, sizeof *out);
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
+  if (!text && len) {
+    ctx->err = "hbam_parse_sam: no text";
+    return HBAM_E_ARG;
+  }
+  hbam::Pipeline& p = *pipe_of(ctx);
+  auto failed = [&](int rc) {
+    ctx->err = p.error();
+    return rc;
+  };
+  int rc;
+  if (ctx->sam_dict == hbam_ctx::SamDict::kUnset) {
+    if ((rc = p.samp_set_dict(ctx->f ? ctx->f->ref_names() : std::vector<std::string>())) != HBAM_OK) return failed(rc);
+    ctx->sam_dict = hbam_ctx::SamDict::kFile;
+  }
+  uint64_t n = 0, consumed = 0, bytes = 0, bad = ~0ull;
+  if ((rc = p.samp_lines(static_cast<const uint8_t*>(text), len, final != 0, &n, &consumed)) != HBAM_OK)
+    return failed(rc);
+  if ((rc = p.samp_measure(n, &bytes, &bad)) != HBAM_OK) return failed(rc);
+  if (bad != ~0ull) {
+    const uint32_t field = (uint32_t)(bad & 0xff);
+    const char* name = hbam::samp_field_name(field);
+    ctx->err = "line " + std::to_string(bad >> 8) + " " + name + (name[0] >= 'A' && name[0] <= 'Z' ? " is malformed" : "") +
+               " (hbam_parse_sam)";
+    return HBAM_E_FORMAT;
+  }
+  if ((rc = p.samp_write(n, bytes)) != HBAM_OK) return failed(rc);
+  out->n = n;
+  out->bytes = bytes;
+  out->consumed = consumed;
+  out->enc = p.samp_enc();
+  out->offs = p.samp_offs();
+  return HBAM_OK;
+}
+
+int hbam_parse_sam_times(hbam_ctx* ctx, float ms[4]) {
+  if (!pipe_of(ctx)) return HBAM_E_STATE;
+  for (int i = 0; i < 4; ++i) ms[i] = pipe_of(ctx)->samp_times()[i];
+  return HBAM_OK;
+}
+
+int hbam_sam_header_to_bam(const void* text, uint64_t l_text, uint8_t** hdr, uint64_t* len) {
+  *hdr = nullptr;
+  *len = 0;
+  if (l_text > 0x7fffffffull || (!text && l_text)) {
+    g_open_err = "hbam_sam_header_to_bam: a header text of at most 2^31 - 1 bytes";
+    return HBAM_E_ARG;
+  }
+  const char* t = static_cast<const char*>(text);
+  std::vector<uint8_t> refs;
+  auto put_i32 = [](std::vector<uint8_t>& v, uint32_t x) {
+    for (int b = 0; b < 4; ++b) v.push_back((uint8_t)(x >> (8 * b)));
+  };
+  uint32_t n_ref = 0;
+  for (uint64_t l0 = 0; l0 < l_text;) {
+    uint64_t l1 = l0;
+    while (l1 < l_text && t[l1] != '\n') ++l1;
+    uint64_t e = l1;
+    if (e > l0 && t[e - 1] == '\r') --e;
+    if (e - l0 >= 4 && memcmp(t + l0, "@SQ\t", 4) == 0) {
+      std::string sn, ln;
+      bool has_sn = false, has_ln = false;
+      for (uint64_t a = l0 + 4; a <= e;) {  // the tab-separated fields behind "@SQ"
+        uint64_t b = a;
+        while (b < e && t[b] != '\t') ++b;
+        if (b - a >= 3 && t[a + 2] == ':') {
+          if (!has_sn && t[a] == 'S' && t[a + 1] == 'N') sn.assign(t + a + 3, b - a - 3), has_sn = true;
+          if (!has_ln && t[a] == 'L' && t[a + 1] == 'N') ln.assign(t + a + 3, b - a - 3), has_ln = true;
+        }
+        a = b + 1;
+      }
+      uint64_t v = 0;
+      bool ok = has_sn && !sn.empty() && has_ln && !ln.empty();
+      for (size_t k = 0; ok && k < ln.size(); ++k) {
+        ok = ln[k] >= '0' && ln[k] <= '9' && v <= 0x7fffffffull;
+        v = v * 10 + (uint64_t)(ln[k] - '0');
+      }
+      if (!ok || v > 0x7fffffffull) {
+        g_open_err = "hbam_sam_header_to_bam: @SQ line " + std::to_string(n_ref) + " lacks SN or a numeric LN";
+        return HBAM_E_FORMAT;
+      }
+      put_i32(refs, (uint32_t)sn.size() + 1);
+      refs.insert(refs.end(), sn.begin(), sn.end());
+      refs.push_back(0);
+      put_i32(refs, (uint32_t)v);
+      ++n_ref;
+    }
+    l0 = l1 + 1;
+  }
+  std::vector<uint8_t> h = {'B', 'A', 'M', 1};
+  put_i32(h, (uint32_t)l_text);
+  h.insert(h.end(), t, t + l_text);
+  put_i32(h, n_ref);
+  h.insert(h.end(), refs.begin(), refs.end());
+  return copy_out(h, hdr, len);
 }
 
 int hbam_sort_writables(hbam_ctx* ctx, int32_t order, uint8_t* out, uint64_t cap, uint64_t* offs, uint32_t* perm,

@@ -235,5 +235,150 @@ HBAM_FMT_HD uint32_t fmt_g(uint32_t bits, Put put) {
 
 HBAM_FMT_HD uint32_t len_g(uint32_t bits) { return fmt_g(bits, NoPut()); }
 
+// ---- the other direction: a decimal text as the nearest 32-bit float ------------
+HBAM_FMT_HD uint32_t big_bits(const Big& a) {  // the bit length (0 for zero)
+  uint32_t r = 0;
+#pragma unroll
+  for (int i = 0; i < kBigWords; ++i)
+    if (a.w[i]) r = 32u * (uint32_t)i + 32u - (uint32_t)__builtin_clz(a.w[i]);
+  return r;
+}
+
+constexpr uint32_t kParseDigits = 19;  // significant digits that enter the value
+
+// The float32 nearest to the decimal get(0) .. get(len - 1), ties to even, with
+// no rounding through a double: false when the text is not
+//   -?digits[.digits][(e|E)[+-]digits]  |  -?.digits[(e|E)[+-]digits]  |  nan  |  inf  |  -inf
+// (nan is 0x7FC00000; hex floats, "infinity", a '+' sign and upper-case
+// specials are refused).  Overflow gives +-inf, underflow denormals or +-0.
+// The first kParseDigits significant digits make the integer D; nonzero digits
+// behind them only say "a little more than D" (a sticky bit).  That is exact
+// for every text of at most 19 significant digits -- all that %g, %.9g,
+// Float.toString and Double.toString print -- and may be one unit off for a
+// longer text whose first 19 digits end exactly on a float or on the midpoint
+// of two.  The value D * 10^E is a ratio of two integers below 2^192 (the
+// powers of 5 go to the numerator or the denominator by E's sign, the powers
+// of 2 into the exponent); a 26-step restoring division gives the 25 or 26
+// leading bits, and those, the remainder and the sticky bit round the 24 (or,
+// for a denormal, fewer) that are kept.
+template <class Get>
+HBAM_FMT_HD bool parse_f32(Get get, uint32_t len, uint32_t* bits) {
+  uint32_t i = 0, sign = 0;
+  if (len == 3 && get(0u) == 'n' && get(1u) == 'a' && get(2u) == 'n') {
+    *bits = 0x7fc00000u;
+    return true;
+  }
+  if (i < len && get(i) == '-') {
+    sign = 0x80000000u;
+    ++i;
+  }
+  if (len - i == 3 && get(i) == 'i' && get(i + 1u) == 'n' && get(i + 2u) == 'f') {
+    *bits = sign | 0x7f800000u;
+    return true;
+  }
+  uint64_t D = 0;
+  uint32_t nd = 0;   // significant digits in D
+  int64_t e10 = 0;
+  bool sticky = false;
+  uint32_t nint = 0, nfrac = 0;
+  for (; i < len; ++i, ++nint) {
+    const uint32_t d = (uint32_t)(uint8_t)get(i) - '0';
+    if (d > 9u) break;
+    if (nd < kParseDigits) {
+      if (D != 0 || d != 0) {
+        D = D * 10u + d;
+        ++nd;
+      }
+    } else {
+      sticky |= d != 0;
+      ++e10;
+    }
+  }
+  if (i < len && get(i) == '.') {
+    for (++i; i < len; ++i, ++nfrac) {
+      const uint32_t d = (uint32_t)(uint8_t)get(i) - '0';
+      if (d > 9u) break;
+      if (nd < kParseDigits) {
+        if (D != 0 || d != 0) {
+          D = D * 10u + d;
+          ++nd;
+        }
+        --e10;
+      } else {
+        sticky |= d != 0;
+      }
+    }
+    if (nfrac == 0) return false;  // "1." and "."
+  } else if (nint == 0) {
+    return false;
+  }
+  if (i < len) {
+    if (get(i) != 'e' && get(i) != 'E') return false;
+    ++i;
+    bool eneg = false;
+    if (i < len && (get(i) == '+' || get(i) == '-')) {
+      eneg = get(i) == '-';
+      ++i;
+    }
+    if (i >= len) return false;
+    int64_t x = 0;
+    for (; i < len; ++i) {
+      const uint32_t d = (uint32_t)(uint8_t)get(i) - '0';
+      if (d > 9u) return false;
+      if (x < 1000000) x = x * 10 + d;  // (saturates far outside the float range)
+    }
+    e10 += eneg ? -x : x;
+  }
+  if (D == 0) {
+    *bits = sign;
+    return true;
+  }
+  // 10^(nd - 1 + e10) <= D * 10^e10 < 10^(nd + e10)
+  const int64_t top = (int64_t)nd + e10;
+  if (top > 39) {  // >= 10^39 > FLT_MAX
+    *bits = sign | 0x7f800000u;
+    return true;
+  }
+  if (top < -45) {  // < 10^-45 < 2^-150, half the smallest denormal
+    *bits = sign;
+    return true;
+  }
+  Big num, den;
+  big_set(num, (uint32_t)D);
+  num.w[1] = (uint32_t)(D >> 32);
+  big_set(den, 1u);
+  if (e10 >= 0) big_mul_pow5(num, (uint32_t)e10); else big_mul_pow5(den, (uint32_t)-e10);  // |e10| <= 64
+  // num / den * 2^sh in (2^24, 2^26)
+  const int sh = 25 - ((int)big_bits(num) - (int)big_bits(den));
+  if (sh >= 0) big_shl(num, (uint32_t)sh); else big_shl(den, (uint32_t)-sh);
+  Big d = den;
+  big_shl(d, 25u);
+  uint32_t q = 0;
+  for (int b = 25; b >= 0; --b) {
+    if (big_cmp(num, d) >= 0) {
+      big_sub(num, d);
+      q |= 1u << b;
+    }
+    big_shr1(d);
+  }
+  const bool rest = sticky || big_bits(num) != 0;
+  const int qb = 32 - (int)__builtin_clz(q);         // 25 or 26
+  const int e = qb - 1 + (int)e10 - sh;              // the value lies in [2^e, 2^(e + 1))
+  const int keep = e >= -126 ? 24 : 24 - (-126 - e);  // mantissa bits kept (a denormal keeps fewer)
+  if (keep < 0) {  // below 2^-150
+    *bits = sign;
+    return true;
+  }
+  const uint32_t drop = (uint32_t)(qb - keep);  // 1 .. 26
+  uint32_t m = q >> drop;
+  const uint32_t low = q & ((1u << drop) - 1u), half = 1u << (drop - 1u);
+  if (low > half || (low == half && (rest || (m & 1u)))) ++m;
+  // a normal m carries its implicit bit into the exponent field; so does a rounding up to 2^24 or 2^23
+  uint32_t r = e >= -126 ? m + ((uint32_t)(e + 126) << 23) : m;
+  if (r >= 0x7f800000u) r = 0x7f800000u;
+  *bits = sign | r;
+  return true;
+}
+
 }  // namespace fmt
 }  // namespace hbam

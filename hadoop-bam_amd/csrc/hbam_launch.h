@@ -214,6 +214,35 @@ hipError_t launch_sam_write(const uint8_t* u, const uint64_t* rec_pos, const Col
                             const uint32_t* ref_off, const uint8_t* ref_bytes, int32_t n_ref,
                             const uint32_t* head_len, const uint64_t* doff, uint64_t total, uint8_t* dst,
                             hipStream_t s);
+// ---- hbam_samparse.hip
+// SAM text into BAM records (hbam_samparse.hip).  text: device, 16 B-aligned,
+// zero from len up to the next multiple of 16 at least; every line ends in
+// '\n' (the host appends the one a final last line lacks).
+// the 4 KiB pieces of len text bytes (one workgroup and one count each)
+uint64_t samp_pieces(uint64_t len);
+// temporary storage of an exclusive sum over m u64 entries
+hipError_t samp_scan_bytes(uint64_t m, size_t* bytes);
+hipError_t launch_samp_scan(void* tmp, size_t tmp_bytes, const uint64_t* in, uint64_t m, uint64_t* out,
+                            hipStream_t s);
+// cnt[p] = the '\n's of piece p, cnt[samp_pieces(len)] = 0
+hipError_t launch_samp_count(const uint8_t* text, uint64_t len, uint64_t* cnt, hipStream_t s);
+// first = the exclusive sum of cnt; start[0] = 0, start[k + 1] = the byte behind the k-th '\n' (n + 1 u64)
+hipError_t launch_samp_starts(const uint8_t* text, uint64_t len, const uint64_t* first, uint64_t* start,
+                              hipStream_t s);
+// The dictionary: dict_n names sorted as unsigned bytes (a prefix first), name j
+// = dict_bytes[dict_off[j], dict_off[j + 1]), dict_idx[j] = its reference index.
+// rlen[i] = the bytes of line i's record (rlen: n + 1 u64, the last 0); *bad
+// (preset ~0) = line << 8 | field of the first malformed line (atomicMin: the
+// lowest line, and its lowest field code; samp_field_name names it)
+hipError_t launch_samp_measure(const uint8_t* text, const uint64_t* start, uint64_t n, const uint32_t* dict_off,
+                               const uint8_t* dict_bytes, const int32_t* dict_idx, int32_t dict_n, uint64_t* rlen,
+                               unsigned long long* bad, hipStream_t s);
+// dst[roff[i], roff[i + 1]) = line i's record; roff = the exclusive sum of rlen.
+// Only after a launch_samp_measure of the same text that left *bad = ~0.
+hipError_t launch_samp_write(const uint8_t* text, const uint64_t* start, uint64_t n, const uint32_t* dict_off,
+                             const uint8_t* dict_bytes, const int32_t* dict_idx, int32_t dict_n, const uint64_t* roff,
+                             uint8_t* dst, hipStream_t s);
+const char* samp_field_name(uint32_t field);
 // ---- hbam_names.hip
 // Queryname order (hbam_names.hip): the name = name_len bytes at base +
 // name_pos, zero-extended and compared as unsigned bytes, then the tie word

@@ -1759,6 +1759,128 @@ int Pipeline::sam_write(const SpanDev& s, uint64_t bytes, uint8_t* dst, float* m
   return kOk;
 }
 
+int Pipeline::samp_set_dict(const std::vector<std::string>& names) {
+  HIPCHK(hipSetDevice(device_));
+  // sorted as unsigned bytes (std::string's order), equal names by index: the first of a run stays
+  std::vector<int32_t> order(names.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return names[a] < names[b]; });
+  std::vector<uint32_t> off(1, 0);
+  std::vector<int32_t> idx;
+  std::string bytes;
+  for (size_t k = 0; k < order.size(); ++k) {
+    if (k && names[order[k]] == names[order[k - 1]]) continue;
+    bytes += names[order[k]];
+    if (bytes.size() > 0xffffffffull) return fail(kErrArg, "reference names longer than 4 GiB");
+    off.push_back((uint32_t)bytes.size());
+    idx.push_back(order[k]);
+  }
+  own(samp_text_, samp_tmp_, samp_rec_, samp_dict_bytes_, samp_cnt_, samp_first_, samp_start_, samp_rlen_,
+      samp_roff_, samp_bad_, samp_dict_off_, samp_dict_idx_);
+  SAMALLOC(samp_dict_off_.reserve(off.size()));
+  SAMALLOC(samp_dict_idx_.reserve(idx.size() + 1));
+  SAMALLOC(samp_dict_bytes_.reserve(bytes.size() + 1));
+  HIPCHK(hipMemcpyAsync(samp_dict_off_.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, stream_));
+  if (!idx.empty()) {
+    HIPCHK(hipMemcpyAsync(samp_dict_idx_.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream_));
+    if (!bytes.empty())
+      HIPCHK(hipMemcpyAsync(samp_dict_bytes_.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, stream_));
+  }
+  HIPCHK(hipStreamSynchronize(stream_));  // (the host vectors go away)
+  samp_dict_n_ = (int32_t)idx.size();
+  return kOk;
+}
+
+int Pipeline::samp_lines(const uint8_t* text, uint64_t len, bool final, uint64_t* n, uint64_t* consumed) {
+  *n = *consumed = 0;
+  for (float& m : samp_ms_) m = 0;
+  samp_len_ = 0;
+  if (samp_dict_n_ < 0) return fail(kErrState, "no dictionary set");
+  // what is parsed: through the last '\n'; a final text's last line gets the '\n' it lacks
+  uint64_t use = len;
+  while (use && text[use - 1] != '\n') --use;
+  const bool add = final && use < len;
+  if (add) use = len;
+  *consumed = use;
+  const uint64_t dlen = use + (add ? 1 : 0);
+  if (dlen == 0) return kOk;
+  HIPCHK(hipSetDevice(device_));
+  const uint64_t np = samp_pieces(dlen);
+  // zero behind the text to the end of its last piece: the aligned 16-byte loads read there
+  SAMALLOC(samp_text_.reserve(np * 4096 + 64));
+  SAMALLOC(samp_cnt_.reserve(np + 1));
+  SAMALLOC(samp_first_.reserve(np + 1));
+  SAMALLOC(samp_bad_.reserve(1));
+  size_t tmp = 0;
+  HIPCHK(samp_scan_bytes(np + 1, &tmp));
+  SAMALLOC(samp_tmp_.reserve(tmp));
+  HIPCHK(hipMemcpyAsync(samp_text_.p, text, use, hipMemcpyHostToDevice, stream_));
+  HIPCHK(hipMemsetAsync(samp_text_.p + use, 0, np * 4096 + 64 - use, stream_));
+  if (add) HIPCHK(hipMemsetAsync(samp_text_.p + use, '\n', 1, stream_));
+  HIPCHK(hipEventRecord(ev_[0], stream_));
+  HIPCHK(launch_samp_count(samp_text_.p, dlen, samp_cnt_.p, stream_));
+  HIPCHK(launch_samp_scan(samp_tmp_.p, tmp, samp_cnt_.p, np + 1, samp_first_.p, stream_));
+  uint64_t lines = 0;
+  HIPCHK(rb(&lines, samp_first_.p + np, 8, stream_));
+  HIPCHK(rb_sync(stream_));
+  if (lines >= 0x7fffffffull) return fail(kErrArg, "too many lines to parse in one call");
+  SAMALLOC(samp_start_.reserve(lines + 1));
+  HIPCHK(launch_samp_starts(samp_text_.p, dlen, samp_first_.p, samp_start_.p, stream_));
+  HIPCHK(hipEventRecord(ev_[1], stream_));
+  samp_len_ = dlen;
+  *n = lines;
+  return kOk;
+}
+
+int Pipeline::samp_measure(uint64_t n, uint64_t* bytes, uint64_t* bad) {
+  *bytes = 0;
+  *bad = ~0ull;
+  if (n == 0) return kOk;
+  if (samp_len_ == 0 || samp_dict_n_ < 0) return fail(kErrState, "no text was split into lines");
+  HIPCHK(hipSetDevice(device_));
+  size_t tmp = 0;
+  HIPCHK(samp_scan_bytes(n + 1, &tmp));
+  SAMALLOC(samp_tmp_.reserve(tmp));
+  SAMALLOC(samp_rlen_.reserve(n + 1));
+  SAMALLOC(samp_roff_.reserve(n + 1));
+  HIPCHK(hipMemsetAsync(samp_bad_.p, 0xff, sizeof(unsigned long long), stream_));
+  HIPCHK(hipEventRecord(ev_[2], stream_));
+  HIPCHK(launch_samp_measure(samp_text_.p, samp_start_.p, n, samp_dict_off_.p, samp_dict_bytes_.p, samp_dict_idx_.p,
+                             samp_dict_n_, samp_rlen_.p, samp_bad_.p, stream_));
+  HIPCHK(hipEventRecord(ev_[3], stream_));
+  HIPCHK(launch_samp_scan(samp_tmp_.p, tmp, samp_rlen_.p, n + 1, samp_roff_.p, stream_));
+  HIPCHK(hipEventRecord(ev_[4], stream_));
+  unsigned long long b = ~0ull;
+  HIPCHK(rb(&b, samp_bad_.p, sizeof b, stream_));
+  HIPCHK(rb(bytes, samp_roff_.p + n, 8, stream_));
+  HIPCHK(rb_sync(stream_));
+  *bad = b;
+  return kOk;
+}
+
+int Pipeline::samp_write(uint64_t n, uint64_t bytes) {
+  samp_enc_.clear();  // (nothing to keep when the tables grow)
+  samp_offs_.clear();
+  if (samp_offs_.resize(n + 1) != hipSuccess || samp_enc_.resize(bytes ? bytes : 1) != hipSuccess)
+    return fail(kErrNoMem, "page-locked memory for the parsed records");
+  samp_offs_[0] = 0;
+  if (n == 0) return kOk;
+  HIPCHK(hipSetDevice(device_));
+  SAMALLOC(samp_rec_.reserve(bytes + 16));
+  HIPCHK(hipEventRecord(ev_[5], stream_));
+  HIPCHK(launch_samp_write(samp_text_.p, samp_start_.p, n, samp_dict_off_.p, samp_dict_bytes_.p, samp_dict_idx_.p,
+                           samp_dict_n_, samp_roff_.p, samp_rec_.p, stream_));
+  HIPCHK(hipEventRecord(ev_[6], stream_));
+  HIPCHK(hipMemcpyAsync(samp_enc_.data(), samp_rec_.p, bytes, hipMemcpyDeviceToHost, stream_));
+  HIPCHK(hipMemcpyAsync(samp_offs_.data(), samp_roff_.p, (n + 1) * 8, hipMemcpyDeviceToHost, stream_));
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipEventElapsedTime(&samp_ms_[0], ev_[0], ev_[1]));
+  HIPCHK(hipEventElapsedTime(&samp_ms_[1], ev_[2], ev_[3]));
+  HIPCHK(hipEventElapsedTime(&samp_ms_[2], ev_[3], ev_[4]));
+  HIPCHK(hipEventElapsedTime(&samp_ms_[3], ev_[5], ev_[6]));
+  return kOk;
+}
+
 namespace {
 hipError_t name_readback(void* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
   Pipeline* p = static_cast<Pipeline*>(ctx);

@@ -405,6 +405,29 @@ class Pipeline {
   int sam_measure(const SpanDev& span, uint64_t* bytes, uint64_t* bad, float* ms2 = nullptr);
   int sam_write(const SpanDev& span, uint64_t bytes, uint8_t* dst, float* ms1 = nullptr);
   const uint64_t* sam_offsets() const { return sam_doff_.p; }
+  // SAM text into BAM records (hbam_samparse.hip), one record per line.
+  // samp_set_dict: the reference names RNAME / RNEXT resolve against, uploaded
+  // as a table sorted for the kernels' binary search (a name that appears twice
+  // keeps its lowest index); samp_has_dict: one was set.  samp_lines: the text
+  // up to its last '\n' (final: all of it, a '\n' added behind a last line that
+  // lacks one) goes to the device and its lines are found; *n = the lines,
+  // *consumed = the text bytes they take.  samp_measure: every line validated
+  // and measured, the scan; *bytes = the encodings' size, *bad = line << 8 |
+  // field code (samp_field_name) of the first malformed line (~0: none).
+  // samp_write: the records, only after a samp_measure that found nothing
+  // malformed; they and their n + 1 starts land in page-locked host memory that
+  // stays valid until the next samp_write: samp_enc(), samp_offs().
+  // samp_times: HIP-event ms of the line finding, the measure pass, the scan
+  // and the write pass of the last samp_write (0 where nothing ran).  A failed
+  // device allocation: kErrNoMem.
+  int samp_set_dict(const std::vector<std::string>& names);
+  bool samp_has_dict() const { return samp_dict_n_ >= 0; }
+  int samp_lines(const uint8_t* text, uint64_t len, bool final, uint64_t* n, uint64_t* consumed);
+  int samp_measure(uint64_t n, uint64_t* bytes, uint64_t* bad);
+  int samp_write(uint64_t n, uint64_t bytes);
+  const uint8_t* samp_enc() const { return samp_enc_.data(); }
+  const uint64_t* samp_offs() const { return samp_offs_.data(); }
+  const float* samp_times() const { return samp_ms_; }
   // SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) of n values
   // framed by offs in host memory (value i = buf[offs[i], offs[i+1]), the
   // last ends at len): SoA columns + keys; out->n stops at the first bad value.
@@ -683,6 +706,18 @@ class Pipeline {
   DevBuf<uint64_t> sam_llen_, sam_doff_;
   DevBuf<unsigned long long> sam_bad_;
   int32_t sam_n_ref_ = -1;  // -1: no table uploaded yet
+  // SAM parse: the text, the '\n' counts of its pieces and their sum, the line starts, the record sizes
+  // and starts, the first bad line, hipcub storage, the records; the sorted dictionary; the host copies
+  DevBuf<uint8_t> samp_text_, samp_tmp_, samp_rec_, samp_dict_bytes_;
+  DevBuf<uint64_t> samp_cnt_, samp_first_, samp_start_, samp_rlen_, samp_roff_;
+  DevBuf<unsigned long long> samp_bad_;
+  DevBuf<uint32_t> samp_dict_off_;
+  DevBuf<int32_t> samp_dict_idx_;
+  int32_t samp_dict_n_ = -1;  // -1: no dictionary uploaded yet
+  uint64_t samp_len_ = 0;     // the text bytes on the device
+  HostTable<uint8_t> samp_enc_;
+  HostTable<uint64_t> samp_offs_;
+  float samp_ms_[4] = {0, 0, 0, 0};
   hipEvent_t ev_[8];
   std::vector<hipEvent_t> tev_;     // timing events of overlapped inflate chunks
 

@@ -60,6 +60,10 @@ class BaiSummary(C.Structure):
     _fields_ = [("n_ref", i32), ("has_no_coor", i32), ("start_of_last_linear_bin", i64), ("no_coor_count", u64)]
 
 
+class SamRecords(C.Structure):
+    _fields_ = [("n", u64), ("bytes", u64), ("consumed", u64), ("enc", P), ("offs", P)]
+
+
 class GpuStats(C.Structure):
     _fields_ = [("n_blocks", u64), ("compressed_bytes", u64), ("inflated_bytes", u64), ("records", u64),
                 ("first_voff", u64), ("last_voff", u64), ("key_xor", u64), ("voff_sum", u64),
@@ -135,6 +139,10 @@ _sig("hbam_gpu_fetch", C.c_int, [P, P, P, u64])
 _sig("hbam_encode_writables", C.c_int, [P, P, u64, P, C.POINTER(u64)])
 _sig("hbam_sort_writables", C.c_int, [P, i32, P, u64, P, P, C.POINTER(u64)])
 _sig("hbam_format_sam", C.c_int, [P, P, u64, P, C.POINTER(u64)])
+_sig("hbam_parse_sam_dict", C.c_int, [P, C.POINTER(C.c_char_p), i32])
+_sig("hbam_parse_sam", C.c_int, [P, P, u64, i32, C.POINTER(SamRecords)])
+_sig("hbam_parse_sam_times", C.c_int, [P, C.POINTER(C.c_float)])
+_sig("hbam_sam_header_to_bam", C.c_int, [P, u64, C.POINTER(P), C.POINTER(u64)])
 _sig("hbam_decode_writables", C.c_int, [P, P, u64, P, u64, C.POINTER(Batch)])
 _sig("hbam_open_codec", C.c_int, [C.POINTER(Opts), C.POINTER(P)])
 _sig("hbam_sort_name_counters", C.c_int, [P, C.POINTER(u64)])
@@ -284,6 +292,22 @@ def bai_query(bai: bytes, intervals):
         _L.hbam_free(out)
 
 
+def sam_header_to_bam(text: bytes) -> bytes:
+    """hbam_sam_header_to_bam (host code, no GPU): the BAM header bytes (magic,
+    l_text, the text verbatim, one reference per @SQ line from SN and LN) of a
+    SAM header text."""
+    text = bytes(text)
+    out = P()
+    n = u64()
+    rc = _L.hbam_sam_header_to_bam(C.c_char_p(text), len(text), C.byref(out), C.byref(n))
+    if rc != OK:
+        raise HbamError(rc, _L.hbam_last_error(None).decode(errors="replace"))
+    try:
+        return C.string_at(out, n.value)
+    finally:
+        _L.hbam_free(out)
+
+
 def _stats_dict(st):
     return {f: getattr(st, f) for f, _ in GpuStats._fields_}
 
@@ -332,7 +356,8 @@ class PinnedBuffer:
 
 
 class _Merge:
-    """hbam_merge_*: the merge of sorted runs of SAMRecordWritable encodings
+    """What Codec and BamFile share on the ctx self._h: hbam_parse_sam* (SAM
+    text into records) and hbam_merge_*: the merge of sorted runs of SAMRecordWritable encodings
     on the ctx self._h (Hadoop's reduce-side merge; shared by Codec and
     BamFile).  The runs' bytes stay in host memory; the order is planned and
     every part gathered on the GPU."""
@@ -344,6 +369,38 @@ class _Merge:
         """Raise the ctx's error unless rc is OK (BamFile and Codec share it)."""
         if rc != OK:
             raise self._err(rc)
+
+    def parse_sam_dict(self, names):
+        """hbam_parse_sam_dict: the reference names parse_sam resolves RNAME and
+        RNEXT against (bytes or str, in dictionary order); None restores a
+        file ctx's own dictionary."""
+        if names is None:
+            self._ok(_L.hbam_parse_sam_dict(self._h, None, -1))
+            return
+        names = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        self._ok(_L.hbam_parse_sam_dict(self._h, arr, len(names)))
+
+    def parse_sam(self, text, final=True):
+        """hbam_parse_sam of SAM alignment lines (bytes, bytearray, memoryview
+        or a NumPy uint8 array), parsed on the GPU: (enc bytes, offs[u64, n +
+        1], consumed) -- the records as BAMRecordCodec.encode writes them, back
+        to back, their starts, and the text bytes used (with final=False the
+        part behind the last newline is left for the next call)."""
+        buf = text if isinstance(text, np.ndarray) else np.frombuffer(text, np.uint8)
+        buf = np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+        r = SamRecords()
+        rc = _L.hbam_parse_sam(self._h, buf.ctypes.data if len(buf) else None, len(buf), int(bool(final)), C.byref(r))
+        self._ok(rc)
+        enc = C.string_at(r.enc, r.bytes) if r.bytes else b""
+        offs = np.frombuffer(C.string_at(r.offs, 8 * (r.n + 1)), np.uint64).copy()
+        return enc, offs, int(r.consumed)
+
+    def parse_sam_times(self):
+        """hbam_parse_sam_times: HIP-event ms of (lines, measure, scan, write) of the last parse_sam."""
+        ms = (C.c_float * 4)()
+        self._ok(_L.hbam_parse_sam_times(self._h, ms))
+        return list(ms)
 
     def merge_begin(self, order="key"):
         rc = _L.hbam_merge_begin(self._h, SORT_ORDERS.get(order, order))

@@ -451,6 +451,99 @@ int hbam_sort_writables(hbam_ctx *ctx, int32_t order, uint8_t *out, uint64_t cap
  * batches), or a last batch from hbam_query_next or hbam_decode_writables.
  * n >= 2^31 - 1 -> HBAM_E_ARG.  A failed device allocation -> HBAM_E_NOMEM. */
 int hbam_format_sam(hbam_ctx *ctx, uint8_t *out, uint64_t cap, uint64_t *offs, uint64_t *len);
+/* ---- SAM text in ---- */
+/* The other direction: SAMRecordReader / [htsjdk] SAMLineParser (the text input
+ * of AnySAMInputFormat, SAMInputFormat; `samtools view -b`) of the alignment
+ * lines in text[0, len), parsed on the GPU.  Record i is line i as [htsjdk]
+ * BAMRecordCodec.encode writes it -- block_size, the 32 fixed bytes, the rest:
+ * the encoding hbam_encode_writables writes and hbam_decode_writables,
+ * hbam_merge_add_run and a BAM writer take.
+ * Lines: a line ends at '\n'; one '\r' directly before it is dropped.  With
+ * final == 0 the bytes behind the last '\n' are not parsed and *consumed stops
+ * before them (the caller carries them into its next chunk); with final != 0 a
+ * last line without a newline is parsed too.  Every line is a record line, one
+ * that starts with '@' too (read names may): as htsjdk stops reading header
+ * lines at the first line that is not one, the caller strips only the leading
+ * run of '@' lines.
+ * Parsing is always strict; there is no stringency.  Every violation below is
+ * HBAM_E_FORMAT, hbam_last_error names the lowest bad "line K " (0-based within
+ * the call) and its field, and out->n is 0.
+ *   fields   at least 11, separated by '\t'; none empty, an aux field from a
+ *            doubled or trailing tab included; an empty line is an error
+ *   decimals an optional '-', then one or more digits; leading zeros allowed,
+ *            '+' not; overflow detected for any number of digits
+ *    1 QNAME  1 to 254 bytes, stored with a NUL; "*" is stored as "*\0"
+ *             (l_read_name 2), as the specification and both writers do
+ *    2 FLAG   0..65535
+ *    3 RNAME  "*" -> -1, else a name of the dictionary (below); unknown -> error
+ *    4 POS    a decimal in [-2^31, 2^31 - 1], stored minus 1 as a wrapping 32-bit
+ *             value: everything hbam_format_sam prints is accepted
+ *    5 MAPQ   0..255
+ *    6 CIGAR  "*", or number-then-operator pairs: the number present and below
+ *             2^28, the operator of "MIDNSHP=X"; more than 65,535 operators ->
+ *             error (the CG:B:I convention is not applied, as in the formatter)
+ *    7 RNEXT  "*" -> -1, "=" -> ref_id (-1 when RNAME is "*"), else a name
+ *    8 PNEXT  as POS
+ *    9 TLEN   a decimal int32
+ *   10 SEQ    "*" -> l_seq 0 (QUAL must then be "*"), else the letters of
+ *             "=ACMGRSVTWYHKDBN" in either case, '.' -> 15, the high nibble
+ *             first, the last low nibble 0 when l_seq is odd; any other byte is
+ *             an error (htsjdk's rule, not samtools' silent 'N')
+ *   11 QUAL   "*" -> l_seq bytes 0xFF, else exactly l_seq bytes in [33, 126],
+ *             stored minus 33
+ *   bin      0 when ref_id < 0, else reg2bin(pos, end) with arithmetic shifts
+ *            (pos = -1 gives 4680), end = pos + the CIGAR's reference length
+ *            (M D N = X), pos + 1 when flag 0x4 is set or that length is 0
+ *   12+ aux  "TG:t:value", at least 5 bytes; only Z and H may have an empty value
+ *            A   exactly one byte
+ *            i   a decimal in [-2^31, 2^32 - 1], stored in the first type that
+ *                holds it of c [-128, 127], C <= 255, s [-32768, 32767],
+ *                S <= 65535, i, I: htsjdk's BinaryTagCodec rule.  samtools
+ *                prefers the unsigned types; equality with samtools is NOT claimed
+ *            f   a float (below)
+ *            Z H the bytes verbatim plus a NUL (H is not validated, as in the formatter)
+ *            B   a subtype letter of "cCsSiIf", then ",value" per element, each
+ *                in the subtype's range; "B:c" alone is count 0
+ *            any other type letter is an error; duplicate tags are not checked
+ * Floats: -?digits[.digits][(e|E)[+-]digits] or -?.digits[(e|E)[+-]digits], and
+ * "nan" (0x7FC00000), "inf", "-inf"; hex floats, "infinity" and upper-case
+ * specials are errors.  The result is the float32 nearest to the decimal's
+ * exact value, ties to even, with no rounding through a double; overflow gives
+ * +-inf, underflow denormals or +-0.  Only the first 19 significant digits
+ * enter the value, nonzero digits behind them act as a sticky bit: exact for
+ * everything %g, %.9g, Float.toString and Double.toString print; a longer text
+ * whose first 19 digits end exactly on a float or on the midpoint of two may
+ * come out one unit off.
+ * Dictionary: a file ctx resolves names against its binary dictionary;
+ * hbam_parse_sam_dict replaces it with n_ref names (names == NULL with n_ref ==
+ * -1 restores the file's).  A codec ctx (hbam_open_codec) with none set accepts
+ * only "*" as RNAME and "*" or "=" as RNEXT.  A name that appears twice resolves
+ * to its lowest index.
+ * The calls work on a file ctx and on a codec ctx and leave the ctx's last batch
+ * untouched (hbam_format_sam still serves it).  out->enc (the records back to
+ * back, out->bytes of them) and out->offs (n + 1 starts, offs[n] == bytes) are
+ * page-locked host memory the ctx owns: valid until the next hbam_parse_sam on
+ * it or its close.  No kernel reads outside [text, text + len) and the zeroed
+ * padding the upload provides.
+ * n >= 2^31 - 1 lines -> HBAM_E_ARG; a failed device allocation -> HBAM_E_NOMEM. */
+typedef struct {
+  uint64_t n;          /* records parsed = complete lines consumed */
+  uint64_t bytes;      /* size of enc */
+  uint64_t consumed;   /* text bytes used: through the last complete line */
+  const uint8_t  *enc; /* the records back to back, ctx-owned page-locked host memory */
+  const uint64_t *offs;/* n + 1 starts, offs[n] == bytes */
+} hbam_sam_records;
+int hbam_parse_sam_dict(hbam_ctx *ctx, const char *const *names, int32_t n_ref);
+int hbam_parse_sam(hbam_ctx *ctx, const void *text, uint64_t len, int32_t final, hbam_sam_records *out);
+/* HIP-event milliseconds of the last hbam_parse_sam on ctx: the line finding,
+ * the measure pass, the scan of the record sizes, the write pass (0 where
+ * nothing ran).  For measuring. */
+int hbam_parse_sam_times(hbam_ctx *ctx, float ms[4]);
+/* The BAM header of a SAM header text (host only, no handle): "BAM\1", l_text,
+ * the text verbatim, n_ref and one entry per @SQ line in order, its name from
+ * SN and its length from LN.  A missing SN, or a missing or non-numeric LN ->
+ * HBAM_E_FORMAT (hbam_last_error(NULL)).  *hdr is released with hbam_free. */
+int hbam_sam_header_to_bam(const void *text, uint64_t l_text, uint8_t **hdr, uint64_t *len);
 /* SAMRecordWritable.readFields (SAMRecordWritable.java:65-68) for n serialized
  * values at once: value i = buf[offs[i], offs[i+1]) (the last ends at len), as
  * the shuffle frames them.  Decodes into out like hbam_decode_span (voff =
