@@ -459,6 +459,17 @@ int hbam_chain_counters(hbam_ctx* ctx, uint64_t out[4]) {
   return ctx->f->pipe().chain_counters(out) == 0 ? HBAM_OK : HBAM_E_DEVICE;
 }
 
+int hbam_chain_lists(hbam_ctx* ctx, uint64_t** g, uint64_t** x, uint32_t** wcnt, uint16_t** list, uint64_t* n_blocks,
+                     uint64_t* n_list, uint32_t* stage) {
+  *stage = 0;
+  *g = *x = nullptr;
+  *wcnt = nullptr;
+  *list = nullptr;
+  *n_blocks = *n_list = 0;
+  if (!ctx || !ctx->f) return HBAM_E_STATE;
+  return chain_lists(*ctx->f, g, x, wcnt, list, n_blocks, n_list, stage);
+}
+
 int hbam_decode_span_device(hbam_ctx* ctx, uint64_t vstart, uint64_t vend, int32_t flags, hbam_gpu_stats* st) {
   if (!ctx || !ctx->f) return HBAM_E_STATE;
   reset_cursors(ctx);

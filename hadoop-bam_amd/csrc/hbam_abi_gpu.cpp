@@ -129,6 +129,27 @@ int decode_device(BamFile& f, uint64_t vstart, uint64_t vend, int32_t flags, hba
   if (rc != HBAM_OK) st->status = rc;
   return rc != HBAM_OK ? rc : st->status;
 }
+
+// hbam_chain_lists: Pipeline::chain_lists into malloc'ed arrays for the caller
+int chain_lists(BamFile& f, uint64_t** g, uint64_t** x, uint32_t** wcnt, uint16_t** list, uint64_t* n_blocks,
+                uint64_t* n_list, uint32_t* stage) {
+  std::vector<uint64_t> gv, xv;
+  std::vector<uint32_t> wv;
+  std::vector<uint16_t> lv;
+  if (f.pipe().chain_lists(&gv, &xv, &wv, &lv, stage) != 0) return HBAM_E_DEVICE;
+  int rc = copy_out(gv, g, n_blocks);
+  if (rc == HBAM_OK) rc = copy_out(xv, x, n_blocks);
+  if (rc == HBAM_OK) rc = copy_out(wv, wcnt, n_blocks);
+  if (rc == HBAM_OK) rc = copy_out(lv, list, n_list);
+  if (rc != HBAM_OK) {
+    for (void* p : {(void*)*g, (void*)*x, (void*)*wcnt, (void*)*list}) free(p);
+    *g = *x = nullptr;
+    *wcnt = nullptr;
+    *list = nullptr;
+    *n_blocks = *n_list = 0;
+  }
+  return rc;
+}
 }  // namespace hbam_abi
 
 namespace {

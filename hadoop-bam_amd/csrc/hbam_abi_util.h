@@ -84,4 +84,7 @@ inline void sort_name_counters(const hbam::Pipeline& p, uint64_t out[3]) {
 // hbam_decode_span_device / hbam_gpu_run (hbam_abi_gpu.cpp)
 int decode_device(BamFile& f, uint64_t vstart, uint64_t vend, int32_t flags, hbam_gpu_stats* st, hbam::SpanDev* last,
                   std::string* err);
+// hbam_chain_lists (hbam_abi_gpu.cpp, with the measurement-only entry points)
+int chain_lists(BamFile& f, uint64_t** g, uint64_t** x, uint32_t** wcnt, uint16_t** list, uint64_t* n_blocks,
+                uint64_t* n_list, uint32_t* stage);
 }  // namespace hbam_abi

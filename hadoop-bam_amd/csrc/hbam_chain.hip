@@ -1,6 +1,6 @@
 // hbam_chain.hip -- gfx950 kernels of the BAM record-boundary chain.
 //
-//   rec_cand / rec_walk / rec_search / rec_linkfix / rec_check   BAM
+//   rec_cand / rec_walk / rec_walk_wave / rec_search / rec_linkfix / rec_check   BAM
 //        record-boundary chain ([htsjdk] BAMRecordCodec.decode;
 //        SplittingBAMIndexer.java:340-368) with the STRICT isValid rules
 #include <hip/hip_runtime.h>
@@ -669,6 +669,13 @@ __global__ void k_rec_emit(ChainEnv E, const uint64_t* __restrict__ entry, const
 //                  listed as a u16 offset.  All walks of a span are in flight
 //                  at once, so the span costs one dependent-load chain of
 //                  ~records-per-block steps instead of a wave per block.
+//   k_rec_walk_wave  the unforced round of the two above in one launch, one
+//                  wave per block: a lane per 4 KiB segment walks from the
+//                  segment's first plausible start, and the lists are stitched
+//                  where the chain from the candidate meets them (the same g,
+//                  x, wcnt, lists and cand).  k_rec_cand + k_rec_walk remain
+//                  as its A/B (kStageWalkLane); k_rec_walk also runs the
+//                  forced re-walk rounds.
 //   k_rec_linkfix  max-scan link check; blocks whose list is off the chain are
 //                  re-walked from their true entry (usually zero or a few).
 //   k_rec_check_out  one wave per block: the reader / indexer rules of
@@ -684,37 +691,47 @@ __global__ void k_rec_emit(ChainEnv E, const uint64_t* __restrict__ entry, const
 // long-read block (C4: the first record start lies ~32 KB in on average)
 // takes 8x fewer dependent steps (0.74 ms per C4 pass before).
 constexpr int kCandPos = 8;
-template <int MODE>
-__global__ __launch_bounds__(64) void k_rec_cand(ChainEnv E, uint64_t* __restrict__ cand) {
-  const uint32_t k = E.k0 + blockIdx.x;
-  const BlockInfo b = E.blocks[k];
-  const uint64_t bend = b.ustart + b.isize;
+// The scan as a wave-level function: the first plausible2 position of [lo,
+// bend), kNone when there is none; wave-uniform arguments, the same result
+// on every lane.  STEPS consecutive 512-position steps have their loads in
+// flight together (one round trip for STEPS steps; k_rec_walk_wave scans
+// long-read blocks 4 steps at a time) and are then tested in order.
+template <int STEPS>
+__device__ __forceinline__ uint64_t cand_scan_wave(const ChainEnv& E, uint64_t lo, uint64_t bend) {
   const uint32_t lane = lane_id();
-  uint64_t c = kNone;
-  if (bend > E.p0 && b.ustart > E.p0 && b.ustart < E.q_end && b.isize > 0) {
-    const uint64_t s0 = b.ustart & ~7ull;  // 8-aligned scan origin (positions < ustart are masked)
-    for (uint64_t c0 = s0; c0 < bend; c0 += 64 * kCandPos) {
-      const uint64_t p0 = c0 + (uint64_t)lane * kCandPos;
-      uint32_t pass = 0;  // bit j: position p0 + j passes the prefilter
-      if (p0 < bend) {
-        uint32_t w[10];
-        const uint2* src = reinterpret_cast<const uint2*>(E.u + p0);  // du_ is padded past the stream
+  const uint64_t s0 = lo & ~7ull;  // 8-aligned scan origin (positions < lo are masked)
+  for (uint64_t c00 = s0; c00 < bend; c00 += (uint64_t)STEPS * 64 * kCandPos) {
+    uint32_t passes[STEPS];  // bit j: position p0 + j of that step passes the prefilter
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-          const uint2 v = src[i];
-          w[2 * i] = v.x;
-          w[2 * i + 1] = v.y;
-        }
+    for (int t = 0; t < STEPS; ++t) {
+      const uint64_t p0 = c00 + (uint64_t)t * 64 * kCandPos + (uint64_t)lane * kCandPos;
+      uint32_t pass = 0;
+      uint32_t w[10];
+      // (a step past the block end loads the origin's bytes and passes nothing: no
+      // branch around the loads, so that the steps' loads go out together)
+      const uint2* src = reinterpret_cast<const uint2*>(E.u + (p0 < bend ? p0 : s0));  // du_ is padded past the stream
 #pragma unroll
-        for (int j = 0; j < kCandPos; ++j) {
-          const uint64_t q = p0 + j;
-          const int32_t ref = (int32_t)__builtin_amdgcn_alignbyte(w[2 + (j >> 2)], w[1 + (j >> 2)], j & 3);
-          const int32_t nref = (int32_t)__builtin_amdgcn_alignbyte(w[7 + (j >> 2)], w[6 + (j >> 2)], j & 3);
-          const bool ok = q >= b.ustart && q < bend &&
-                          (q + 36 > E.e_inf || (ref >= -1 && ref < E.n_ref && nref >= -1 && nref < E.n_ref));
-          pass |= ok ? 1u << j : 0u;
-        }
+      for (int i = 0; i < 5; ++i) {
+        const uint2 v = src[i];
+        w[2 * i] = v.x;
+        w[2 * i + 1] = v.y;
       }
+#pragma unroll
+      for (int j = 0; j < kCandPos; ++j) {
+        const uint64_t q = p0 + j;
+        const int32_t ref = (int32_t)__builtin_amdgcn_alignbyte(w[2 + (j >> 2)], w[1 + (j >> 2)], j & 3);
+        const int32_t nref = (int32_t)__builtin_amdgcn_alignbyte(w[7 + (j >> 2)], w[6 + (j >> 2)], j & 3);
+        const bool ok = (q >= lo) & (q < bend) &
+                        ((q + 36 > E.e_inf) | ((ref >= -1) & (ref < E.n_ref) & (nref >= -1) & (nref < E.n_ref)));
+        pass |= ok ? 1u << j : 0u;
+      }
+      passes[t] = pass;
+    }
+#pragma unroll
+    for (int t = 0; t < STEPS; ++t) {
+      const uint64_t c0 = c00 + (uint64_t)t * 64 * kCandPos;
+      const uint64_t p0 = c0 + (uint64_t)lane * kCandPos;
+      const uint32_t pass = passes[t];
       uint32_t hit = kCandPos;  // the first position of this lane that is plausible2
       if (__ballot(pass != 0)) {
         for (uint32_t m = pass; m; m &= m - 1) {
@@ -728,35 +745,100 @@ __global__ __launch_bounds__(64) void k_rec_cand(ChainEnv E, uint64_t* __restric
       const uint64_t hm = __ballot(hit < kCandPos);
       if (hm) {
         const uint32_t f = (uint32_t)__ffsll((long long)hm) - 1;
-        c = c0 + (uint64_t)f * kCandPos + (uint32_t)__shfl((int)hit, (int)f, 64);
-        break;
-      }
-    }
-    // A start 1-3 bytes before a true record reads that record's block_size
-    // shifted up by whole bytes (~2^8-2^24 times it) and, with refID 0, its
-    // fields stay in range: plausible2 passes and the walk leaves the block
-    // at once -- past the inflated end of a window it cannot be checked, and
-    // the link check then re-walks the block and the ones its far exit hid
-    // (one round each; C2 passes took two, drop-in windows fell back to the
-    // serial link).  When c's record leaves the block, a plausible2 start
-    // 1-3 bytes later whose record ends inside the block is taken instead.
-    if (c != kNone && lane == 0 && c + 4 + (uint64_t)(int32_t)ldu32(E.u, c) >= bend) {
-      for (uint32_t d = 1; d <= 3; ++d) {
-        const uint64_t q = c + d;
-        if (q + 36 <= E.e_inf && q + 4 + (uint64_t)(int32_t)ldu32(E.u, q) < bend && plausible2(E, q)) {
-          c = q;
-          break;
-        }
+        return c0 + (uint64_t)f * kCandPos + (uint32_t)__shfl((int)hit, (int)f, 64);
       }
     }
   }
-  if (lane == 0) cand[blockIdx.x] = c;
+  return kNone;
+}
+
+// A start 1-3 bytes before a true record reads that record's block_size
+// shifted up by whole bytes (~2^8-2^24 times it) and, with refID 0, its
+// fields stay in range: plausible2 passes and the walk leaves the block
+// at once -- past the inflated end of a window it cannot be checked, and
+// the link check then re-walks the block and the ones its far exit hid
+// (one round each; C2 passes took two, drop-in windows fell back to the
+// serial link).  When c's record leaves the block, a plausible2 start
+// 1-3 bytes later whose record ends inside the block is taken instead.
+// (One lane's work; c != kNone.)
+__device__ __forceinline__ uint64_t cand_shift(const ChainEnv& E, uint64_t c, uint64_t bend) {
+  if (c + 4 + (uint64_t)(int32_t)ldu32(E.u, c) >= bend) {
+    for (uint32_t d = 1; d <= 3; ++d) {
+      const uint64_t q = c + d;
+      if (q + 36 <= E.e_inf && q + 4 + (uint64_t)(int32_t)ldu32(E.u, q) < bend && plausible2(E, q)) return q;
+    }
+  }
+  return c;
+}
+
+// the blocks that get a candidate: past the span's first block, inside the span
+__device__ __forceinline__ bool cand_wanted(const ChainEnv& E, const BlockInfo& b) {
+  return b.ustart + b.isize > E.p0 && b.ustart > E.p0 && b.ustart < E.q_end && b.isize > 0;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64) void k_rec_cand(ChainEnv E, uint64_t* __restrict__ cand) {
+  const BlockInfo b = E.blocks[E.k0 + blockIdx.x];
+  const uint64_t bend = b.ustart + b.isize;
+  uint64_t c = kNone;
+  if (cand_wanted(E, b)) {
+    c = cand_scan_wave<1>(E, b.ustart, bend);
+    if (c != kNone && lane_id() == 0) c = cand_shift(E, c, bend);
+  }
+  if (lane_id() == 0) cand[blockIdx.x] = c;
 }
 
 constexpr int kGuessLookahead = 4;  // plausible records required past a guess walk's exit
 constexpr uint64_t kRetry = ~0ull - 2;  // g[]: the candidate's walk failed, search on
 constexpr uint32_t kListPlausible = 0x80000000u;  // wcnt flag: the list came from a plausible() walk
 constexpr uint32_t kListCountMask = 0x7fffffffu;
+
+// The plausible walk from `start`, shared by k_rec_walk's guess branch and
+// the pieces of k_rec_walk_wave: every record must pass plausible(); the
+// records that start before lim are listed (put(index, position)).  With lim
+// == bend (the block end) the walk goes on for kGuessLookahead records past
+// the block end, or to the end of the stream or of the inflated range; with
+// lim < bend it ends at the first record start at or past lim.  exitq = that
+// first start at or past lim, n = the records listed.
+// Software-pipelined: record q's read-name end byte and the next record's
+// head are loaded together (plausible_head), one dependent round trip per
+// record.  Loads past the inflated range read the stream's padding and are
+// not used (plausible_head's rules).
+struct PlausWalk {
+  bool valid;
+  uint64_t exitq;
+  uint32_t n;
+};
+template <typename Put>
+__device__ __forceinline__ PlausWalk walk_plausible(const ChainEnv& E, uint64_t start, uint64_t lim, uint64_t bend,
+                                                    Put put) {
+  uint64_t q = start, exitq = start;
+  uint32_t m = 0;
+  bool valid = true;
+  // (a start past the inflated range -- an exit handed on for its lookahead --
+  // is not read: the loop ends before it looks at h)
+  RecHead h = load_head(E.u, start + 4 <= E.e_inf ? start : 0);
+  int left = kGuessLookahead;  // plausible records required past the block end
+  for (;;) {
+    const bool inside = q < lim;
+    if (!inside && (lim < bend || left-- <= 0 || q == E.e_true || q + 36 > E.e_inf)) break;
+    uint64_t na = q;
+    const int ph = plausible_head(E, q, h, &na);
+    const uint64_t q2 = q + 4 + (uint64_t)(int32_t)h.at(0);
+    const uint8_t nb = E.u[na];
+    // (q2 may lie anywhere: its head is loaded when its block_size is
+    // inflated; reads reach 40 bytes past it, inside the stream's pad)
+    h = load_head(E.u, q2 + 4 <= E.e_inf ? q2 : q);
+    if (ph == 0 || (ph == 2 && nb != 0)) { valid = false; break; }
+    if (inside) {
+      put(m, q);
+      ++m;
+      exitq = q2;  // the first record start at or past lim (the walk's exit)
+    }
+    q = q2;
+  }
+  return PlausWalk{valid, exitq, m};
+}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __restrict__ cand,
@@ -828,38 +910,13 @@ __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __
     } else {
       const uint64_t c = cand[i];
       if (c < bend) {  // c == kNone (no candidate): nothing to walk
-        // software-pipelined: record q's read-name end byte and the next
-        // record's head are loaded together (plausible_head), one dependent
-        // round trip per record.  Loads past the inflated range read the
-        // stream's padding and are not used (plausible_head's rules).
-        uint64_t q = c, exitq = c;
-        uint32_t m = 0;
-        bool valid = true;
-        RecHead h = load_head(E.u, q);
-        int left = kGuessLookahead;  // plausible records required past the block end
-        for (;;) {
-          const bool inside = q < bend;
-          if (!inside && (left-- <= 0 || q == E.e_true || q + 36 > E.e_inf)) break;
-          uint64_t na = q;
-          const int ph = plausible_head(E, q, h, &na);
-          const uint64_t q2 = q + 4 + (uint64_t)(int32_t)h.at(0);
-          const uint8_t nb = E.u[na];
-          // (q2 may lie anywhere: its head is loaded when its block_size is
-          // inflated; reads reach 40 bytes past it, inside the stream's pad)
-          h = load_head(E.u, q2 + 4 <= E.e_inf ? q2 : q);
-          if (ph == 0 || (ph == 2 && nb != 0)) { valid = false; break; }
-          if (inside) {
-            if (m < kListCap) L[m] = (uint16_t)(q - b.ustart);
-            ++m;
-            exitq = q2;  // the first record start past the block (the walk's exit)
-          }
-          q = q2;
-        }
-        q = exitq;
-        if (valid) {
+        const PlausWalk w = walk_plausible(E, c, bend, bend, [&](uint32_t m, uint64_t q) {
+          if (m < kListCap) L[m] = (uint16_t)(q - b.ustart);
+        });
+        if (w.valid) {
           g = c;
-          x = q;
-          n = m;
+          x = w.exitq;
+          n = w.n;
           plaus_list = true;
         } else {
           g = kRetry;  // later candidates: k_rec_search (wave per block)
@@ -872,6 +929,219 @@ __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __
   g_out[i] = g;
   x_out[i] = x;
   wcnt[i] = n | (plaus_list ? kListPlausible : 0u);
+}
+
+// ---------------------------------------------------------------------------
+// k_rec_walk_wave: the unforced round of k_rec_cand + k_rec_walk, one wave per
+// block.  The chain from a block's candidate c is deterministic (the record at
+// q names the next start), so a walk begun at any record start on it lists
+// what the walk from c lists from there on.  The block is cut into kWalkSeg-
+// byte segments counted from its start:
+//   probe   every lane tests kCandPos positions of the first kWalkProbe bytes
+//           of every segment against the refID prefilter (all segments' loads
+//           in flight together); lane j then takes the first of segment j's
+//           positions that is plausible2: c_j.  c_0 is the block's candidate
+//           (cand_scan_wave over the rest of the block when segment 0's
+//           window holds none), moved by cand_shift: what k_rec_cand writes.
+//   walk    lane j runs walk_plausible from c_j (the segment holding c: from
+//           c) up to the next segment's start, listing into its LDS row; the
+//           last segment's walker also walks the lookahead past the block.
+//   stitch  wave-uniform: cur = c; while cur is inside the block, walker k of
+//           the segment holding cur is taken when c_k == cur (kRetry when it
+//           met an implausible record: that record is on the chain from c),
+//           else the whole wave walks on from cur to the end of segment k.
+//           When the last piece did not end at the block end, the lookahead
+//           is walked from the exit.
+// g, x, wcnt, list, cand and the overflow word are those of the two kernels
+// it replaces (tests/walk_wave_model.py restates the stitch; its test and
+// tests/test_gpu_walk_wave.py hold the two equal).
+// (experiment variants: make EXTRA="-DHBAM_WALK_SEG=... -DHBAM_WALK_WAVES=...")
+#ifndef HBAM_WALK_SEG
+#define HBAM_WALK_SEG 4096
+#endif
+#ifndef HBAM_WALK_WAVES
+#define HBAM_WALK_WAVES 4
+#endif
+constexpr uint32_t kWalkSeg = HBAM_WALK_SEG;
+constexpr uint32_t kWalkSegs = kMaxIsize / kWalkSeg;  // segments of the largest block
+constexpr uint32_t kWalkProbe = 64 * kCandPos;        // positions probed per segment
+constexpr uint32_t kSegListCap = kWalkSeg / 32;       // a walker's LDS row: 128 entries
+// a plausible record takes at least 36 bytes (block_size >= 32), so a segment holds fewer starts than a row
+static_assert(kWalkSeg / 36 + 1 < kSegListCap, "a segment's record starts fit its walker's row");
+static_assert(kWalkSegs * kWalkSeg == kMaxIsize && kWalkSegs <= 64 && kWalkSegs % 8 == 0, "a lane per segment");
+static_assert(kWalkProbe <= kWalkSeg, "a probe window inside its segment");
+constexpr uint32_t kPassRow = 64 + 4;  // a segment's 64 pass bytes (+ a word: rows on different banks)
+
+__device__ __forceinline__ uint64_t rfl_u64(uint64_t v) {
+  return (uint64_t)rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32);
+}
+
+// (launch bounds: DESIGN.md 4.3, "k_rec_walk_wave")
+template <int MODE>
+__global__ __launch_bounds__(64, HBAM_WALK_WAVES) void k_rec_walk_wave(ChainEnv E, uint64_t* __restrict__ cand,
+                                                         uint64_t* __restrict__ g_out, uint64_t* __restrict__ x_out,
+                                                         uint32_t* __restrict__ wcnt, uint16_t* __restrict__ list,
+                                                         uint32_t* __restrict__ overflow) {
+  __shared__ uint16_t s_list[kWalkSegs][kSegListCap];
+  __shared__ __attribute__((aligned(4))) uint8_t s_pass[kWalkSegs][kPassRow];
+  const uint32_t i = blockIdx.x, lane = lane_id();
+  const BlockInfo b = E.blocks[E.k0 + i];
+  const uint64_t bend = b.ustart + b.isize;
+  uint16_t* __restrict__ L = list + (uint64_t)i * kListCap;
+  uint64_t g = kNone, x = kNone, c = kNone;
+  uint32_t n = 0;
+  bool plaus_list = false;
+  const bool live = bend > E.p0 && b.ustart < E.q_end && b.isize > 0;
+  if (live && b.ustart <= E.p0) {
+    // the block of the span start: the entry is known, the walk goes by
+    // block_size alone (chain_step).  One lane's chain of dependent loads:
+    // the wave pulls the block into L2 first with independent loads, as a
+    // forced re-walk does, so that the other blocks' waves do not wait on it.
+    uint32_t acc = 0;
+    const uint64_t hi = min(bend + 4096, E.e_inf);
+    for (uint64_t a = (b.ustart & ~127ull) + 128ull * lane; a < hi; a += 128ull * 64) acc += ldu32(E.u, a);
+    if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
+    if (lane == 0) {
+      g = E.p0;
+      uint64_t q = E.p0, nq;
+      while (q < bend) {
+        if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
+        ++n;
+        if (!chain_step<MODE>(E, q, &nq)) break;
+        q = nq;
+      }
+      x = q;
+    }
+  } else if (live) {
+    const uint32_t nseg = min((b.isize + kWalkSeg - 1) / kWalkSeg, kWalkSegs);
+    // ---- probe: the prefilter over every segment's window, 8 segments' loads at a time
+#pragma unroll
+    for (uint32_t j0 = 0; j0 < kWalkSegs; j0 += 8) {
+      U32x4 wa[8], wb[8];
+#pragma unroll
+      for (uint32_t t = 0; t < 8; ++t) {
+        const uint64_t p0 = b.ustart + (uint64_t)(j0 + t) * kWalkSeg + (uint64_t)lane * kCandPos;
+        const uint8_t* src = E.u + ((p0 < bend ? p0 : b.ustart) & ~3ull);  // (the stream is padded past its end)
+        wa[t] = *reinterpret_cast<const U32x4*>(src + 4);   // refID of p0 .. p0 + 7
+        wb[t] = *reinterpret_cast<const U32x4*>(src + 24);  // next refID of the same
+      }
+#pragma unroll
+      for (uint32_t t = 0; t < 8; ++t) {
+        const uint64_t p0 = b.ustart + (uint64_t)(j0 + t) * kWalkSeg + (uint64_t)lane * kCandPos;
+        const uint32_t sh = (uint32_t)(p0 & 3);
+        // the dwords at p0 + 4 (+ 4, + 8) and at p0 + 24 (+ 4, + 8)
+        const uint32_t r0 = __builtin_amdgcn_alignbyte(wa[t].y, wa[t].x, sh), r1 = __builtin_amdgcn_alignbyte(wa[t].z, wa[t].y, sh),
+                       r2 = __builtin_amdgcn_alignbyte(wa[t].w, wa[t].z, sh);
+        const uint32_t m0 = __builtin_amdgcn_alignbyte(wb[t].y, wb[t].x, sh), m1 = __builtin_amdgcn_alignbyte(wb[t].z, wb[t].y, sh),
+                       m2 = __builtin_amdgcn_alignbyte(wb[t].w, wb[t].z, sh);
+        uint32_t pass = 0;  // bit k: position p0 + k passes the prefilter
+#pragma unroll
+        for (int k = 0; k < kCandPos; ++k) {
+          const uint64_t q = p0 + k;
+          const int32_t ref = (int32_t)__builtin_amdgcn_alignbyte(k < 4 ? r1 : r2, k < 4 ? r0 : r1, k & 3);
+          const int32_t nref = (int32_t)__builtin_amdgcn_alignbyte(k < 4 ? m1 : m2, k < 4 ? m0 : m1, k & 3);
+          const bool ok = (q < bend) & ((q + 36 > E.e_inf) | ((ref >= -1) & (ref < E.n_ref) & (nref >= -1) & (nref < E.n_ref)));
+          pass |= ok ? 1u << k : 0u;
+        }
+        s_pass[j0 + t][lane] = (uint8_t)(j0 + t < nseg ? pass : 0u);
+      }
+    }
+    __syncthreads();
+    // ---- lane j: the first plausible2 position of segment j's window
+    // (every lane first finds its next passing position in LDS, then the
+    // lanes run plausible2 together: its dependent loads are in flight for
+    // all segments at once.  A lane whose position fails goes round again;
+    // with a plausible2 per lane as it met its position, the lanes' three
+    // round trips each ran one after another: 0.76 ms per C2 pass.)
+    uint64_t cj = kNone;
+    {
+      const uint64_t sj = b.ustart + (uint64_t)lane * kWalkSeg;
+      const uint32_t* row = reinterpret_cast<const uint32_t*>(s_pass[lane < nseg ? lane : 0]);
+      bool scanning = lane < nseg;
+      uint32_t w = 0, m = 0;  // m: the bits of word w - 1 not looked at yet (bit k: position sj + 32 (w - 1) + k)
+      for (;;) {
+        uint64_t q = kNone;
+        if (scanning) {
+          while (m == 0 && w < 16) m = row[w++];
+          if (m) {
+            q = sj + 32 * (w - 1) + ((uint32_t)__ffs((int)m) - 1);
+            m &= m - 1;
+          } else {
+            scanning = false;
+          }
+        }
+        if (__ballot(q != kNone) == 0) break;
+        if (q != kNone && plausible2(E, q)) {
+          cj = q;
+          scanning = false;
+        }
+      }
+    }
+    // ---- the block's candidate (k_rec_cand's)
+    c = shfl_u64(cj, 0);
+    if (c == kNone && b.isize > kWalkProbe) c = cand_scan_wave<4>(E, b.ustart + kWalkProbe, bend);
+    c = rfl_u64(c);
+    if (c != kNone) c = rfl_u64(cand_shift(E, c, bend));
+    if (c != kNone) {
+      // ---- walk: lane j from its segment's start
+      const uint32_t k0 = min((uint32_t)((c - b.ustart) / kWalkSeg), nseg - 1);
+      const uint64_t start = lane == k0 ? c : lane > k0 && lane < nseg ? cj : kNone;
+      const uint64_t lim = lane + 1 < nseg ? b.ustart + (uint64_t)(lane + 1) * kWalkSeg : bend;
+      PlausWalk w{false, kNone, 0};
+      if (start != kNone) {
+        uint16_t* row = s_list[lane];
+        w = walk_plausible(E, start, lim, bend, [&](uint32_t m, uint64_t q) {
+          if (m < kSegListCap) row[m] = (uint16_t)(q - b.ustart);
+        });
+      }
+      __syncthreads();
+      // ---- stitch
+      uint64_t cur = c;
+      bool ok = true, looked = false;
+      while (cur < bend) {
+        const uint32_t k = min((uint32_t)((cur - b.ustart) / kWalkSeg), nseg - 1);
+        const uint64_t klim = k + 1 < nseg ? b.ustart + (uint64_t)(k + 1) * kWalkSeg : bend;
+        uint32_t pn;
+        if (rfl_u64(shfl_u64(start, k)) == cur) {  // walker k is on the chain
+          ok = rfl((uint32_t)__shfl((int)w.valid, (int)k, 64)) != 0;
+          pn = rfl((uint32_t)__shfl((int)w.n, (int)k, 64));
+          if (ok) {
+            for (uint32_t t = lane; t < min(pn, kSegListCap); t += 64)
+              if (n + t < kListCap) L[n + t] = s_list[k][t];
+            cur = rfl_u64(shfl_u64(w.exitq, k));
+            // (a row too short: only in a block above kMaxIsize, which locate refuses; the count path then)
+            if (pn > kSegListCap && lane == 0) atomicOr(overflow, 1u);
+          }
+        } else {  // off it (or no start in its window): the wave walks on through segment k
+          const PlausWalk s = walk_plausible(E, cur, klim, bend, [&](uint32_t m, uint64_t q) {
+            if (lane == 0 && n + m < kListCap) L[n + m] = (uint16_t)(q - b.ustart);
+          });
+          ok = rfl((uint32_t)s.valid) != 0;
+          pn = rfl(s.n);
+          cur = rfl_u64(s.exitq);
+        }
+        if (!ok) break;
+        n += pn;
+        looked = klim == bend;  // that piece walked the lookahead
+      }
+      if (ok && !looked) ok = rfl((uint32_t)walk_plausible(E, cur, bend, bend, [](uint32_t, uint64_t) {}).valid) != 0;
+      if (ok) {
+        g = c;
+        x = cur;
+        plaus_list = true;
+      } else {
+        g = kRetry;  // later candidates: k_rec_search (wave per block)
+        n = 0;
+      }
+    }
+  }
+  if (lane == 0) {
+    if (n > kListCap) atomicOr(overflow, 1u);
+    cand[i] = c;
+    g_out[i] = g;
+    x_out[i] = x;
+    wcnt[i] = n | (plaus_list ? kListPlausible : 0u);
+  }
 }
 
 // Blocks whose first candidate failed (k_rec_walk: g == kRetry): one wave
@@ -1250,12 +1520,18 @@ hipError_t launch_chain(const ChainArgs& a, int mode, int stage, hipStream_t s) 
                            a.rec_pos, a.rec_voff);
       });
       break;
-    case kStageWalk:  // candidates + walks
+    case kStageWalk:      // candidates + walks, a wave per block
+    case kStageWalkLane:  // the same by k_rec_cand + a lane per block (HBAM_CHAIN_WALK=lane)
       with_mode(mode, [&](auto m) {
         constexpr int M = decltype(m)::value;
-        hipLaunchKernelGGL(k_rec_cand<M>, dim3(nb), dim3(64), 0, s, E, a.cand);
-        hipLaunchKernelGGL(k_rec_walk<M>, dim3((nb + 255) / 256), dim3(256), 0, s, E, a.cand, nullptr, a.g, a.x,
-                           a.wcnt, a.list, a.counters + 2, false);
+        if (stage == kStageWalk) {
+          hipLaunchKernelGGL(k_rec_walk_wave<M>, dim3(nb), dim3(64), 0, s, E, a.cand, a.g, a.x, a.wcnt, a.list,
+                             a.counters + 2);
+        } else {
+          hipLaunchKernelGGL(k_rec_cand<M>, dim3(nb), dim3(64), 0, s, E, a.cand);
+          hipLaunchKernelGGL(k_rec_walk<M>, dim3((nb + 255) / 256), dim3(256), 0, s, E, a.cand, nullptr, a.g, a.x,
+                             a.wcnt, a.list, a.counters + 2, false);
+        }
         hipLaunchKernelGGL(k_rec_search<M>, dim3(nb), dim3(64), 0, s, E, a.cand, a.g, a.x, a.wcnt, a.list,
                            a.counters + 2, a.counters + kChainCtrSearched);
       });

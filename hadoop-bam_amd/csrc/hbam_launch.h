@@ -53,7 +53,8 @@ enum ChainStage : int {
   kStageSerialLink = 1,  // exact serial link over the walk exits (entry[] + summary)
   kStageCount = 2,       // per-block count + validation by walking (list overflow path)
   kStageEmit = 3,        // per-block positions + voffs by walking (list overflow path)
-  kStageWalk = 5,        // candidates + lane-per-block walks
+  kStageWalkLane = 4,    // candidates (k_rec_cand) + lane-per-block walks: kStageWalk's result, the A/B of it
+  kStageWalk = 5,        // candidates + walks, a wave per block (k_rec_walk_wave), then the search
   kStageLinkCheck = 6,   // max-scan link check with re-walk requests
   kStageRewalk = 7,      // re-walk the requested blocks (entries validated)
   kStageRewalkAll = 8,   // re-walk every block off the serial link's entry[]

@@ -81,6 +81,9 @@ Pipeline::Pipeline(int device) : device_(device) {
       sort_iota_, sort_perm_, sort_tmp_, name_pos_, name_census_, name_len_, name_tie_, seg_anchor_, seg_exit_, seg_cnt_, seg_off_);
   if (const char* e = getenv("HBAM_LOCATE_SEG")) locate_seg_ = strtoull(e, nullptr, 0);
   if (const char* e = getenv("HBAM_NAME_FULL_PASSES")) name_full_ = strtoull(e, nullptr, 0) != 0;
+  if (const char* e = getenv("HBAM_CHAIN_WALK")) walk_lane_ = strcmp(e, "lane") == 0;
+  if (const char* e = getenv("HBAM_CHAIN_KEEP_WALK")) keep_walk_ = strtoull(e, nullptr, 0) != 0;
+  own(kept_g_, kept_x_, kept_wcnt_, kept_list_);
   for (auto& e : ev_) (void)hipEventCreate(&e);
   for (auto& e : sync_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   for (auto& e : tab_ev_) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
@@ -402,6 +405,29 @@ int Pipeline::chain_counters(uint64_t out[4]) {
   out[0] = w[kChainCtrSearched - kChainCtr];
   out[1] = w[kChainCtrRewalked - kChainCtr];
   out[2] = w[kChainCtrDropped - kChainCtr];
+  return kOk;
+}
+
+int Pipeline::chain_lists(std::vector<uint64_t>* g, std::vector<uint64_t>* x, std::vector<uint32_t>* wcnt,
+                          std::vector<uint16_t>* list, uint32_t* stage) {
+  const uint32_t nb = kept_nb_;
+  *stage = nb ? kept_stage_ : 0;
+  g->assign(nb, 0);
+  x->assign(nb, 0);
+  wcnt->assign(nb, 0);
+  list->clear();
+  if (!nb) return kOk;  // no record pass yet, or nothing kept
+  HIPCHK(hipSetDevice(device_));
+  std::vector<uint16_t> all((size_t)nb * kListCap);
+  HIPCHK(hipStreamSynchronize(stream_));
+  HIPCHK(hipMemcpy(g->data(), kept_g_.p, (size_t)nb * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(x->data(), kept_x_.p, (size_t)nb * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(wcnt->data(), kept_wcnt_.p, (size_t)nb * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(all.data(), kept_list_.p, all.size() * 2, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < nb; ++i) {
+    const uint32_t n = std::min((*wcnt)[i] & 0x7fffffffu, kListCap);  // (kListCountMask)
+    list->insert(list->end(), all.begin() + (size_t)i * kListCap, all.begin() + (size_t)i * kListCap + n);
+  }
   return kOk;
 }
 
@@ -1254,7 +1280,19 @@ int Pipeline::span_scratch(SpanPass& s) {
   a.scan_bytes = lsb;
   HIPCHK(hipMemsetAsync(need_.p, 0, 8, stream_));
   HIPCHK(hipMemsetAsync(counters_.p, 0, kChainCtr * 4, stream_));  // the per-pass words only
-  HIPCHK(launch_chain(a, s.mode, kStageWalk, stream_));  // candidates + lane-per-block walks
+  HIPCHK(launch_chain(a, s.mode, walk_lane_ ? kStageWalkLane : kStageWalk, stream_));  // candidates + walks
+  if (keep_walk_) {  // (measurement: chain_lists)
+    HIPCHK(kept_g_.reserve(nb));
+    HIPCHK(kept_x_.reserve(nb));
+    HIPCHK(kept_wcnt_.reserve(nb));
+    HIPCHK(kept_list_.reserve((uint64_t)nb * kListCap));
+    HIPCHK(hipMemcpyAsync(kept_g_.p, g_.p, (size_t)nb * 8, hipMemcpyDeviceToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(kept_x_.p, x_.p, (size_t)nb * 8, hipMemcpyDeviceToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(kept_wcnt_.p, wcnt_.p, (size_t)nb * 4, hipMemcpyDeviceToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(kept_list_.p, list_.p, (size_t)nb * kListCap * 2, hipMemcpyDeviceToDevice, stream_));
+    kept_nb_ = nb;
+    kept_stage_ = walk_lane_ ? kStageWalkLane : kStageWalk;
+  }
   return kOk;
 }
 

@@ -499,6 +499,13 @@ class Pipeline {
   // check re-walked from a forced entry, out[2] = stray walks it dropped,
   // out[3] = link-check rounds
   int chain_counters(uint64_t out[4]);
+  // What the walk stage of the last record pass left, before any link round
+  // (kept only under HBAM_CHAIN_KEEP_WALK=1; empty otherwise): per block g, x
+  // and wcnt, and in `list` the first wcnt & kListCountMask entries of every
+  // block's list back to back; *stage = the ChainStage that ran (kStageWalk or
+  // kStageWalkLane; 0: nothing kept).  A synchronous read, for tests.
+  int chain_lists(std::vector<uint64_t>* g, std::vector<uint64_t>* x, std::vector<uint32_t>* wcnt,
+                  std::vector<uint16_t>* list, uint32_t* stage);
   StageTimes times;
   bool timing = false;  // record per-stage HIP event times
 
@@ -679,6 +686,13 @@ class Pipeline {
   DevBuf<uint64_t> rcand_, force_;  // chain v2
   DevBuf<uint32_t> wcnt_, counters_;
   DevBuf<uint16_t> list_;
+  // HBAM_CHAIN_WALK=lane: the walk stage by k_rec_cand + a lane per block (the A/B of k_rec_walk_wave);
+  // HBAM_CHAIN_KEEP_WALK=1: a copy of g, x, wcnt and the lists as the walk stage left them (chain_lists)
+  bool walk_lane_ = false, keep_walk_ = false;
+  DevBuf<uint64_t> kept_g_, kept_x_;
+  DevBuf<uint32_t> kept_wcnt_;
+  DevBuf<uint16_t> kept_list_;
+  uint32_t kept_nb_ = 0, kept_stage_ = 0;
   DevBuf<uint32_t> fuse_;  // k_rec_check_out: [0..1] early-stop key (u64), [2] first failing block, [3] last block with records + 1
   DevBuf<uint8_t> scan_tmp_;
   DevBuf<uint8_t> cols_;  // SoA backing store

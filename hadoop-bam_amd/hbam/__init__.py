@@ -109,6 +109,8 @@ _sig("hbam_inflate_token_count", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_path_counts", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_inflate_narrow_counts", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_chain_counters", C.c_int, [P, C.POINTER(u64)])
+_sig("hbam_chain_lists", C.c_int, [P, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(u64),
+                                   C.POINTER(u64), C.POINTER(u32)])
 _sig("hbam_file_stats", C.c_int, [P, C.POINTER(u64), C.POINTER(u64)])
 _sig("hbam_bytes_read", C.c_int, [P, C.POINTER(u64)])
 _sig("hbam_prefetch", C.c_int, [P, u64, u64])
@@ -687,6 +689,26 @@ class BamFile(_Merge):
         rc = _L.hbam_chain_counters(self._h, v)
         self._ok(rc)
         return dict(zip(("searched", "rewalked", "dropped", "link_rounds"), (int(x) for x in v)))
+
+    def chain_lists(self):
+        """What the walk stage of the last record pass left, before the link
+        check (hbam_chain_lists; kept only when HBAM_CHAIN_KEEP_WALK=1 was set
+        at the open): dict of g, x (uint64 per block), wcnt (uint32 per block)
+        and list (uint16: every block's listed offsets back to back), and
+        stage, the launch_chain stage that ran."""
+        ptr = [P() for _ in range(4)]
+        nb, nl, stage = u64(), u64(), u32()
+        rc = _L.hbam_chain_lists(self._h, *(C.byref(p) for p in ptr), C.byref(nb), C.byref(nl), C.byref(stage))
+        self._ok(rc)
+        try:
+            out = {"stage": int(stage.value)}  # 5: a wave per block, 4: k_rec_cand + a lane per block
+            for name, p, dt, n in zip(("g", "x", "wcnt", "list"), ptr, (np.uint64, np.uint64, np.uint32, np.uint16),
+                                      (nb.value, nb.value, nb.value, nl.value)):
+                out[name] = np.frombuffer(C.string_at(p, n * np.dtype(dt).itemsize), dtype=dt).copy()
+            return out
+        finally:
+            for p in ptr:
+                _L.hbam_free(p)
 
     def decode_span_device(self, vstart, vend, timing=False, decode=True, digest=True):
         """The span decoded with the records left in HBM: stats dict."""

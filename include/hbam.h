@@ -756,6 +756,21 @@ int hbam_inflate_narrow_counts(hbam_ctx *ctx, uint64_t out[3]);
  * synchronous, the device counters are read only here. */
 int hbam_chain_counters(hbam_ctx *ctx, uint64_t out[4]);
 
+/* What the walk stage of the ctx's last record pass left, before the link
+ * check saw it: per BGZF block of the pass the walk's start g (~0: none), its
+ * exit x and the list word wcnt (bit 31: a plausible() walk, the rest: the
+ * record starts counted), and in *list the first min(count, 2048) listed
+ * offsets of every block back to back (*n_list of them).  Kept only when
+ * HBAM_CHAIN_KEEP_WALK=1 was in the environment at the open; otherwise, and
+ * before the first pass, *n_blocks = 0.  HBAM_CHAIN_WALK=lane at the open
+ * makes the stage run as k_rec_cand + one lane per block instead of one wave
+ * per block: the two must agree array for array; *stage says which ran (5: a
+ * wave per block, 4: a lane per block, 0: nothing kept).  Measurement and tests (no
+ * reference counterpart); synchronous; every array is the caller's
+ * (hbam_free). */
+int hbam_chain_lists(hbam_ctx *ctx, uint64_t **g, uint64_t **x, uint32_t **wcnt, uint16_t **list,
+                     uint64_t *n_blocks, uint64_t *n_list, uint32_t *stage);
+
 /* The sharded SplittingBAMIndexer.index (SplittingBAMIndexer.java:262-287,
  * SURVEY 8e step 3): the records of FileVirtualSplit [vstart, vend) read
  * under the indexer's rules (readAlignment/fullySkip, :340-368), their count
