@@ -1,8 +1,17 @@
-// hbam_chain.hip -- gfx950 kernels of the BAM record-boundary chain.
-//
-//   rec_cand / rec_walk / rec_walk_wave / rec_search / rec_linkfix / rec_check   BAM
-//        record-boundary chain ([htsjdk] BAMRecordCodec.decode;
-//        SplittingBAMIndexer.java:340-368) with the STRICT isValid rules
+// hbam_chain.hip -- gfx950 kernels of the BAM record-boundary chain ([htsjdk]
+// BAMRecordCodec.decode; SplittingBAMIndexer.java:340-368).  In file order:
+//   the record rules    SAMRecord.isValid under STRICT / LENIENT (one rule
+//                       list around a lane's or a wave's pass over the cigar),
+//                       the dead positions, plausible() for the guesses
+//   k_rec_link          the exact serial link (fallback)
+//   k_rec_emit          positions + voffs by walking (count path)
+//   the walk stage      k_rec_walk_wave (or k_rec_cand + k_rec_walk), then
+//                       k_rec_search: a guessed chain and a record list per block
+//   k_rec_linkfix       the parallel link check; k_rec_walk re-walks what it forces
+//   check_listed_h      the reader / indexer rules per record, for
+//   k_rec_count           the count path (a list overflowed) and
+//   k_rec_check_out       the list path: check + output in one launch
+//   launch_*            the host wrappers (hbam_launch.h)
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stddef.h>
@@ -102,202 +111,170 @@ __device__ bool aux_find(const uint8_t* u, uint64_t a, uint64_t e, uint16_t tag,
   return false;
 }
 
-// true when the (fully inflated) record at q fails validation.  strict =
-// false keeps only the structural decode failures (LENIENT still decodes the
-// cigar for isValid and logs the rest).
-// *defer (when given): a cigar longer than kWaveCigarOps operators is not
-// checked here (false returned, *defer set) -- record_invalid_wave takes it.
-// (h: the record's head, load_head(E.u, q), already in registers)
-__device__ __forceinline__ bool record_invalid_h(const ChainEnv& E, uint64_t q, int32_t bs, bool strict, bool* defer,
-                                                 const RecHead& h) {
-  const uint8_t* u = E.u;
-  const int32_t ref = (int32_t)h.at(1), pos = (int32_t)h.at(2);
+// The rule list, each rule once: the rules that read only the record's head
+// (record_structure_invalid, head_rules_invalid), what a pass over the cigar
+// establishes (CigarFacts; one lane's serial loop or a wave's scans fill it,
+// with one placement rule for both: cigar_op_misplaced), and the rules that
+// consume it (cigar_rules_invalid).  Verdicts are booleans, so the order of
+// the rules is free; what is loaded is not: nothing reads past q + 4 + bs.
+struct RecFields {  // the fixed fields the rules read, off the record's head
+  int32_t ref, pos, lseq, nref, npos;
+  uint32_t lrn, mapq, bin, ncig, flag;
+};
+__device__ __forceinline__ RecFields rec_fields(const RecHead& h) {
   const uint32_t w12 = h.at(3), w16 = h.at(4);
-  const uint32_t lrn = w12 & 0xffu, mapq = (w12 >> 8) & 0xffu, bin = w12 >> 16;
-  const uint32_t ncig = w16 & 0xffffu, flag = w16 >> 16;
-  if (defer && ncig > kWaveCigarOps) {
-    *defer = true;
-    return false;
-  }
-  const int32_t lseq = (int32_t)h.at(5), nref = (int32_t)h.at(6), npos = (int32_t)h.at(7);
-  // structure: the lazy fields isValid decodes must lie inside the record
-  if (lrn < 1 || lseq < 0) return true;
-  const int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + ((int64_t)lseq + 1) / 2 + (int64_t)lseq;
-  if (need > (int64_t)bs) return true;
-  const uint64_t c0 = q + 36 + lrn;
-  uint32_t qlen = 0, rlen = 0;
-  for (uint32_t k = 0; k < ncig; ++k) {
-    const uint32_t op = ldu32(u, c0 + 4ull * k) & 0xfu;
-    if (op > 8) return true;
-  }
-  if (!strict) return false;
-  const bool paired = flag & 0x1, unmapped = flag & 0x4;
-  if (!paired) {
+  RecFields f;
+  f.ref = (int32_t)h.at(1);
+  f.pos = (int32_t)h.at(2);
+  f.lrn = w12 & 0xffu;
+  f.mapq = (w12 >> 8) & 0xffu;
+  f.bin = w12 >> 16;
+  f.ncig = w16 & 0xffffu;
+  f.flag = w16 >> 16;
+  f.lseq = (int32_t)h.at(5);
+  f.nref = (int32_t)h.at(6);
+  f.npos = (int32_t)h.at(7);
+  return f;
+}
+
+// structure: the lazy fields isValid decodes must lie inside the record
+__device__ __forceinline__ bool record_structure_invalid(const RecFields& f, int32_t bs) {
+  if (f.lrn < 1 || f.lseq < 0) return true;
+  const int64_t need = 32 + (int64_t)f.lrn + 4 * (int64_t)f.ncig + ((int64_t)f.lseq + 1) / 2 + (int64_t)f.lseq;
+  return need > (int64_t)bs;
+}
+
+// STRICT: unpaired / paired, unmapped / mapped, position, mate position
+__device__ __forceinline__ bool head_rules_invalid(const ChainEnv& E, const RecFields& f) {
+  const uint32_t flag = f.flag;
+  if (!(flag & 0x1)) {
     if (flag & (0x2 | 0x8 | 0x20 | 0x40 | 0x80)) return true;
-    if (nref != -1) return true;
+    if (f.nref != -1) return true;
   } else {
-    if (nref == -1) {
-      if (npos != -1) return true;
+    if (f.nref == -1) {
+      if (f.npos != -1) return true;
       if (!(flag & 0x8)) return true;  // "Mapped mate should have mate reference name"
     } else {
-      if (npos == -1) return true;
-      if (E.ref_len && (int64_t)npos + 1 > (int64_t)E.ref_len[nref]) return true;
+      if (f.npos == -1) return true;
+      if (E.ref_len && (int64_t)f.npos + 1 > (int64_t)E.ref_len[f.nref]) return true;
     }
     if (!(flag & 0xC0)) return true;  // neither first nor second of pair
   }
-  if (unmapped) {
+  if (flag & 0x4) {
     if (flag & (0x100 | 0x800)) return true;
-    if (mapq != 0) return true;  // (a cigar on an unmapped read is allowed: test.bam has them)
+    if (f.mapq != 0) return true;  // (a cigar on an unmapped read is allowed: test.bam has them)
   } else {
-    if (ncig == 0) return true;
+    if (f.ncig == 0) return true;
     if (E.n_ref == 0) return true;  // MISSING_SEQUENCE_DICTIONARY
   }
-  if (ref == -1) {
-    if (pos != -1) return true;
+  if (f.ref == -1) {
+    if (f.pos != -1) return true;
   } else {
-    if (pos == -1) return true;
-    if (E.ref_len && (int64_t)pos + 1 > (int64_t)E.ref_len[ref]) return true;
-  }
-  // cigar: Cigar.isValid + alignment blocks (mapped reads only)
-  bool real = false;
-  int64_t rpos = (int64_t)pos + 1, maxend = 0;
-  uint32_t prev_op = 99, first_op = 99, last_op = 99;
-  if (ncig) {
-    first_op = ldu32(u, c0) & 0xfu;
-    last_op = ldu32(u, c0 + 4ull * (ncig - 1)) & 0xfu;
-  }
-  // Cigar.isValid: between two separators (M/=/X/N or P) an I or a D may
-  // appear only once ("No M or N operator between pair of I/D operators")
-  bool seen_i = false, seen_d = false;
-  for (uint32_t k = 0; k < ncig; ++k) {
-    const uint32_t c = ldu32(u, c0 + 4ull * k), op = c & 0xfu, len = c >> 4;
-    const bool consumes_read = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;
-    const bool consumes_ref = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
-    if (consumes_read) qlen += len;
-    if (consumes_ref) rlen += len;
-    if (!unmapped) {
-      if (len == 0) return true;
-      if (op == 5) {
-        if (k != 0 && k != ncig - 1) return true;
-      } else if (op == 4) {
-        if (k == 0 || k == ncig - 1) {
-        } else if (k == 1) {
-          if (!(ncig == 3 && last_op == 5) && first_op != 5) return true;
-        } else if (k == ncig - 2) {
-          if (last_op != 5) return true;
-        } else {
-          return true;
-        }
-      } else if (op == 6) {
-        if (k != 0) {
-          if (k == ncig - 1) return true;
-          const uint32_t nx = ldu32(u, c0 + 4ull * (k + 1)) & 0xfu;
-          const bool pr = prev_op <= 3 || prev_op == 7 || prev_op == 8, nr = nx <= 3 || nx == 7 || nx == 8;
-          if (!pr || !nr) return true;
-        }
-        seen_i = seen_d = false;
-      } else {  // real operator
-        real = true;
-        if (op == 1) {
-          if (seen_i) return true;
-          seen_i = true;
-        } else if (op == 2) {
-          if (seen_d) return true;
-          seen_d = true;
-        } else {
-          seen_i = seen_d = false;
-        }
-        if (op == 0 || op == 7 || op == 8) maxend = max(maxend, rpos + (int64_t)len - 1);
-      }
-    }
-    if (consumes_ref) rpos += len;
-    prev_op = op;
-  }
-  if (!unmapped) {
-    if (!real) return true;
-    if (ref >= 0 && E.ref_len && maxend > (int64_t)E.ref_len[ref]) return true;  // CIGAR_MAPS_OFF_REFERENCE
-  }
-  // bin: computeIndexingBin()
-  {
-    const int start0 = pos;  // getAlignmentStart() - 1
-    int end = unmapped ? 0 : (int)((int64_t)pos + 1 + (int64_t)rlen - 1);
-    if (end <= 0) end = start0 + 1;
-    if ((uint32_t)reg2bin_dev(start0, end) != bin) return true;
-  }
-  if (lseq != 0 && ncig != 0 && (int64_t)qlen != (int64_t)lseq) return true;  // MISMATCH_CIGAR_SEQ_LENGTH
-  if (lseq == 0 && !(flag & 0x100)) {  // EMPTY_READ unless FZ, or CQ and CS
-    const uint64_t a0 = c0 + 4ull * ncig, ae = q + 4 + (uint64_t)bs;
-    int64_t zl = -1;
-    if (!aux_find(u, a0, ae, (uint16_t)('F' | ('Z' << 8)), &zl)) {
-      int64_t cq = -1, cs = -1;
-      const bool hq = aux_find(u, a0, ae, (uint16_t)('C' | ('Q' << 8)), &cq);
-      const bool hs = aux_find(u, a0, ae, (uint16_t)('C' | ('S' << 8)), &cs);
-      if (!hq || !hs || cq <= 0 || cs <= 0) return true;
-    }
+    if (f.pos == -1) return true;
+    if (E.ref_len && (int64_t)f.pos + 1 > (int64_t)E.ref_len[f.ref]) return true;
   }
   return false;
 }
 
-__device__ bool record_invalid(const ChainEnv& E, uint64_t q, int32_t bs, bool strict, bool* defer = nullptr) {
-  return record_invalid_h(E, q, bs, strict, defer, load_head(E.u, q));
+// What a pass over the cigar establishes.  bad: an operator above 8 (all a
+// LENIENT pass looks for), or under STRICT a broken Cigar.isValid rule of a
+// mapped read; real: an operator other than S / H / P seen; qlen / rlen: read
+// and reference bases (wrapping u32 sums); maxend: the furthest end of an
+// M / = / X block.
+struct CigarFacts {
+  bool bad, real;
+  uint32_t qlen, rlen;
+  int64_t maxend;
+};
+__device__ __forceinline__ bool op_consumes_read(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
+__device__ __forceinline__ bool op_consumes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
+
+// Cigar.isValid's rules for operator k by itself: a zero length, an H not at
+// an end, an S with more than an H between it and an end, a P at the end or
+// next to an operator that is not M I D N = X.  op_at(j) = operator j (called
+// for a P's two neighbours only).
+template <typename OpAt>
+__device__ __forceinline__ bool cigar_op_misplaced(uint32_t k, uint32_t op, uint32_t len, uint32_t ncig, uint32_t first_op,
+                                                   uint32_t last_op, OpAt op_at) {
+  if (len == 0) return true;
+  if (op == 5) return k != 0 && k != ncig - 1;
+  if (op == 4) {
+    if (k == 0 || k == ncig - 1) return false;
+    if (k == 1) return !(ncig == 3 && last_op == 5) && first_op != 5;
+    if (k == ncig - 2) return last_op != 5;
+    return true;
+  }
+  if (op == 6 && k != 0) {
+    if (k == ncig - 1) return true;
+    const uint32_t pv = op_at(k - 1), nx = op_at(k + 1);
+    const bool pr = pv <= 3 || pv == 7 || pv == 8, nr = nx <= 3 || nx == 7 || nx == 8;
+    return !pr || !nr;
+  }
+  return false;
 }
 
-// record_invalid by a whole wave, for records with long cigars (ONT-like
-// reads carry thousands of operators; one lane walking them serially set the
-// pace of the record check: 2.0 ms per C4 pass).  Same rules, same result: the
-// per-operator rules become a lane-per-operator pass over chunks of 64, the
-// running state becomes scans --
+// CigarFacts by one lane's serial loop (cigars up to kWaveCigarOps operators
+// in k_rec_check_out; any length in k_rec_count)
+__device__ __forceinline__ CigarFacts cigar_facts_lane(const uint8_t* u, uint64_t c0, const RecFields& f, bool strict) {
+  const uint32_t ncig = f.ncig;
+  CigarFacts c{false, false, 0, 0, 0};
+  for (uint32_t k = 0; k < ncig; ++k) {
+    if ((ldu32(u, c0 + 4ull * k) & 0xfu) > 8) {
+      c.bad = true;
+      return c;
+    }
+  }
+  if (!strict) return c;
+  const bool unmapped = f.flag & 0x4;
+  const auto op_at = [&](uint32_t j) { return ldu32(u, c0 + 4ull * j) & 0xfu; };
+  const uint32_t first_op = ncig ? op_at(0) : 99u, last_op = ncig ? op_at(ncig - 1) : 99u;
+  int64_t rpos = (int64_t)f.pos + 1;
+  // Cigar.isValid: between two separators (M/=/X/N or P) an I or a D may
+  // appear only once ("No M or N operator between pair of I/D operators")
+  bool seen_i = false, seen_d = false;
+  for (uint32_t k = 0; k < ncig; ++k) {
+    const uint32_t w = ldu32(u, c0 + 4ull * k), op = w & 0xfu, len = w >> 4;
+    if (op_consumes_read(op)) c.qlen += len;
+    if (op_consumes_ref(op)) c.rlen += len;
+    if (!unmapped) {
+      c.bad = cigar_op_misplaced(k, op, len, ncig, first_op, last_op, op_at) || (op == 1 && seen_i) || (op == 2 && seen_d);
+      if (c.bad) return c;
+      if (op == 6) {
+        seen_i = seen_d = false;
+      } else if (op != 4 && op != 5) {  // real operator
+        c.real = true;
+        if (op == 1) seen_i = true;
+        else if (op == 2) seen_d = true;
+        else seen_i = seen_d = false;
+        if (op == 0 || op == 7 || op == 8) c.maxend = max(c.maxend, rpos + (int64_t)len - 1);
+      }
+    }
+    if (op_consumes_ref(op)) rpos += len;
+  }
+  return c;
+}
+
+// CigarFacts by a whole wave, for records with long cigars (ONT-like reads
+// carry thousands of operators; one lane walking them serially set the pace
+// of the record check: 2.0 ms per C4 pass).  Same facts: the per-operator
+// rules become a lane-per-operator pass over chunks of 64, the running state
+// becomes scans --
 //   qlen / rlen            wrapping u32 sums (as the serial u32 accumulators)
 //   alignment block ends   exclusive 64-bit sum of reference lengths before k
 //   Cigar.isValid I/D pairs   an I (D) is invalid when the previous I (D)
 //                          comes after the last separator (M N = X P) before it:
 //                          two running max-scans of 1-based indices.
-// Wave-uniform arguments; returns the same value on every lane.
-__device__ bool record_invalid_wave(const ChainEnv& E, uint64_t q, int32_t bs, bool strict) {
-  const uint8_t* u = E.u;
-  const uint32_t lane = lane_id();
-  const int32_t ref = (int32_t)ldu32(u, q + 4), pos = (int32_t)ldu32(u, q + 8);
-  const uint32_t w12 = ldu32(u, q + 12), w16 = ldu32(u, q + 16);
-  const uint32_t lrn = w12 & 0xffu, mapq = (w12 >> 8) & 0xffu, bin = w12 >> 16;
-  const uint32_t ncig = w16 & 0xffffu, flag = w16 >> 16;
-  const int32_t lseq = (int32_t)ldu32(u, q + 20), nref = (int32_t)ldu32(u, q + 24), npos = (int32_t)ldu32(u, q + 28);
-  if (lrn < 1 || lseq < 0) return true;
-  const int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + ((int64_t)lseq + 1) / 2 + (int64_t)lseq;
-  if (need > (int64_t)bs) return true;
-  const uint64_t c0 = q + 36 + lrn;
+// Wave-uniform arguments; returns the same facts on every lane.
+__device__ __forceinline__ CigarFacts cigar_facts_wave(const uint8_t* u, uint64_t c0, const RecFields& f, bool strict) {
+  const uint32_t lane = lane_id(), ncig = f.ncig;
+  CigarFacts c{false, false, 0, 0, 0};
   bool bad = false;
   for (uint32_t k = lane; k < ncig; k += 64) bad |= (ldu32(u, c0 + 4ull * k) & 0xfu) > 8;
-  if (__ballot(bad)) return true;
-  if (!strict) return false;
-  const bool paired = flag & 0x1, unmapped = flag & 0x4;
-  if (!paired) {
-    if (flag & (0x2 | 0x8 | 0x20 | 0x40 | 0x80)) return true;
-    if (nref != -1) return true;
-  } else {
-    if (nref == -1) {
-      if (npos != -1) return true;
-      if (!(flag & 0x8)) return true;
-    } else {
-      if (npos == -1) return true;
-      if (E.ref_len && (int64_t)npos + 1 > (int64_t)E.ref_len[nref]) return true;
-    }
-    if (!(flag & 0xC0)) return true;
-  }
-  if (unmapped) {
-    if (flag & (0x100 | 0x800)) return true;
-    if (mapq != 0) return true;
-  } else {
-    if (ncig == 0) return true;
-    if (E.n_ref == 0) return true;
-  }
-  if (ref == -1) {
-    if (pos != -1) return true;
-  } else {
-    if (pos == -1) return true;
-    if (E.ref_len && (int64_t)pos + 1 > (int64_t)E.ref_len[ref]) return true;
-  }
-  const uint32_t first_op = ncig ? ldu32(u, c0) & 0xfu : 99u;
-  const uint32_t last_op = ncig ? ldu32(u, c0 + 4ull * (ncig - 1)) & 0xfu : 99u;
+  c.bad = __ballot(bad) != 0;
+  if (c.bad || !strict) return c;
+  const bool unmapped = f.flag & 0x4;
+  const auto op_at = [&](uint32_t j) { return ldu32(u, c0 + 4ull * j) & 0xfu; };
+  const uint32_t first_op = ncig ? op_at(0) : 99u, last_op = ncig ? op_at(ncig - 1) : 99u;
   uint32_t qlen = 0, rlen = 0;          // lane partial sums (wrapping, as the serial code)
   uint64_t rcarry = 0;                  // reference bases of the chunks before
   uint32_t sep_carry = 0, i_carry = 0, d_carry = 0;  // 1-based indices of the last separator / I / D
@@ -306,14 +283,12 @@ __device__ bool record_invalid_wave(const ChainEnv& E, uint64_t q, int32_t bs, b
   for (uint32_t k0 = 0; k0 < ncig; k0 += 64) {
     const uint32_t k = k0 + lane;
     const bool in = k < ncig;
-    const uint32_t c = in ? ldu32(u, c0 + 4ull * k) : 0u, op = in ? c & 0xfu : 15u, len = c >> 4;
-    const bool consumes_read = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;
-    const bool consumes_ref = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
-    if (consumes_read) qlen += len;
-    if (consumes_ref) rlen += len;
-    const uint64_t rl = consumes_ref ? (uint64_t)len : 0ull;
+    const uint32_t w = in ? ldu32(u, c0 + 4ull * k) : 0u, op = in ? w & 0xfu : 15u, len = w >> 4;
+    if (op_consumes_read(op)) qlen += len;
+    if (op_consumes_ref(op)) rlen += len;
+    const uint64_t rl = op_consumes_ref(op) ? (uint64_t)len : 0ull;
     const uint64_t rincl = wave_incl_sum64(rl);
-    const int64_t rpos = (int64_t)pos + 1 + (int64_t)(rcarry + rincl - rl);  // before op k
+    const int64_t rpos = (int64_t)f.pos + 1 + (int64_t)(rcarry + rincl - rl);  // before op k
     rcarry += (uint64_t)__builtin_amdgcn_readlane((int)(uint32_t)rincl, 63) |
               ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rincl >> 32), 63) << 32);
     // running 1-based indices (0 = none) up to and including op k
@@ -333,29 +308,8 @@ __device__ bool record_invalid_wave(const ChainEnv& E, uint64_t q, int32_t bs, b
     i_carry = (uint32_t)__builtin_amdgcn_readlane((int)i_i, 63);
     d_carry = (uint32_t)__builtin_amdgcn_readlane((int)d_i, 63);
     if (in && !unmapped) {
-      if (len == 0) bad = true;
-      if (op == 5) {
-        if (k != 0 && k != ncig - 1) bad = true;
-      } else if (op == 4) {
-        if (k == 0 || k == ncig - 1) {
-        } else if (k == 1) {
-          if (!(ncig == 3 && last_op == 5) && first_op != 5) bad = true;
-        } else if (k == ncig - 2) {
-          if (last_op != 5) bad = true;
-        } else {
-          bad = true;
-        }
-      } else if (op == 6) {
-        if (k != 0) {
-          if (k == ncig - 1) {
-            bad = true;
-          } else {
-            const uint32_t pv = ldu32(u, c0 + 4ull * (k - 1)) & 0xfu, nx = ldu32(u, c0 + 4ull * (k + 1)) & 0xfu;
-            const bool pr = pv <= 3 || pv == 7 || pv == 8, nr = nx <= 3 || nx == 7 || nx == 8;
-            if (!pr || !nr) bad = true;
-          }
-        }
-      } else {  // real operator
+      if (cigar_op_misplaced(k, op, len, ncig, first_op, last_op, op_at)) bad = true;
+      if (op != 4 && op != 5 && op != 6) {  // real operator
         real = true;
         if (op == 1 && i_x > sep_x) bad = true;  // a second I since the last separator
         if (op == 2 && d_x > sep_x) bad = true;
@@ -363,32 +317,87 @@ __device__ bool record_invalid_wave(const ChainEnv& E, uint64_t q, int32_t bs, b
       }
     }
   }
-  if (__ballot(bad)) return true;
-  qlen = wave_sum_u32(qlen);
-  rlen = wave_sum_u32(rlen);
+  c.bad = __ballot(bad) != 0;
+  c.real = __ballot(real) != 0;
+  c.qlen = wave_sum_u32(qlen);
+  c.rlen = wave_sum_u32(rlen);
+  c.maxend = wave_max_i64(maxend);
+  return c;
+}
+
+// STRICT: the rules on what the cigar pass found
+__device__ __forceinline__ bool cigar_rules_invalid(const ChainEnv& E, uint64_t q, int32_t bs, const RecFields& f,
+                                                    const CigarFacts& c) {
+  const bool unmapped = f.flag & 0x4;
   if (!unmapped) {
-    if (__ballot(real) == 0) return true;
-    maxend = wave_max_i64(maxend);
-    if (ref >= 0 && E.ref_len && maxend > (int64_t)E.ref_len[ref]) return true;
+    if (!c.real) return true;
+    if (f.ref >= 0 && E.ref_len && c.maxend > (int64_t)E.ref_len[f.ref]) return true;  // CIGAR_MAPS_OFF_REFERENCE
   }
+  // bin: computeIndexingBin()
   {
-    const int start0 = pos;
-    int end = unmapped ? 0 : (int)((int64_t)pos + 1 + (int64_t)rlen - 1);
+    const int start0 = f.pos;  // getAlignmentStart() - 1
+    int end = unmapped ? 0 : (int)((int64_t)f.pos + 1 + (int64_t)c.rlen - 1);
     if (end <= 0) end = start0 + 1;
-    if ((uint32_t)reg2bin_dev(start0, end) != bin) return true;
+    if ((uint32_t)reg2bin_dev(start0, end) != f.bin) return true;
   }
-  if (lseq != 0 && ncig != 0 && (int64_t)qlen != (int64_t)lseq) return true;
-  if (lseq == 0 && !(flag & 0x100)) {
-    const uint64_t a0 = c0 + 4ull * ncig, ae = q + 4 + (uint64_t)bs;
+  if (f.lseq != 0 && f.ncig != 0 && (int64_t)c.qlen != (int64_t)f.lseq) return true;  // MISMATCH_CIGAR_SEQ_LENGTH
+  if (f.lseq == 0 && !(f.flag & 0x100)) {  // EMPTY_READ unless FZ, or CQ and CS
+    const uint64_t a0 = q + 36 + f.lrn + 4ull * f.ncig, ae = q + 4 + (uint64_t)bs;
     int64_t zl = -1;
-    if (!aux_find(u, a0, ae, (uint16_t)('F' | ('Z' << 8)), &zl)) {
+    if (!aux_find(E.u, a0, ae, (uint16_t)('F' | ('Z' << 8)), &zl)) {
       int64_t cq = -1, cs = -1;
-      const bool hq = aux_find(u, a0, ae, (uint16_t)('C' | ('Q' << 8)), &cq);
-      const bool hs = aux_find(u, a0, ae, (uint16_t)('C' | ('S' << 8)), &cs);
+      const bool hq = aux_find(E.u, a0, ae, (uint16_t)('C' | ('Q' << 8)), &cq);
+      const bool hs = aux_find(E.u, a0, ae, (uint16_t)('C' | ('S' << 8)), &cs);
       if (!hq || !hs || cq <= 0 || cs <= 0) return true;
     }
   }
   return false;
+}
+
+// true when the (fully inflated) record at q fails validation: the rules
+// above around the given pass over the cigar.  strict = false keeps only the
+// structural decode failures (LENIENT still decodes the cigar for isValid and
+// logs the rest).
+template <typename Facts>
+__device__ __forceinline__ bool record_invalid_by(const ChainEnv& E, uint64_t q, int32_t bs, bool strict, const RecFields& f,
+                                                  Facts cigar_facts) {
+  if (record_structure_invalid(f, bs)) return true;
+  if (strict && head_rules_invalid(E, f)) return true;
+  const CigarFacts c = cigar_facts(E.u, q + 36 + f.lrn, f, strict);
+  if (c.bad) return true;
+  return strict && cigar_rules_invalid(E, q, bs, f, c);
+}
+
+// One lane's verdict.  *defer (when given): a cigar longer than kWaveCigarOps
+// operators is not checked here (false returned, *defer set) --
+// record_invalid_wave takes it.
+// (h: the record's head, load_head(E.u, q), already in registers)
+__device__ __forceinline__ bool record_invalid_h(const ChainEnv& E, uint64_t q, int32_t bs, bool strict, bool* defer,
+                                                 const RecHead& h) {
+  const RecFields f = rec_fields(h);
+  if (defer && f.ncig > kWaveCigarOps) {
+    *defer = true;
+    return false;
+  }
+  return record_invalid_by(E, q, bs, strict, f, [](const uint8_t* u, uint64_t c0, const RecFields& f, bool strict) {
+    return cigar_facts_lane(u, c0, f, strict);
+  });
+}
+
+__device__ __forceinline__ uint64_t rfl_u64(uint64_t v) {
+  return (uint64_t)rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32);
+}
+
+// A whole wave's verdict on one record (wave-uniform arguments, taken as
+// scalars: the record's fields then live in SGPRs beside the caller's
+// per-lane state; the same value on every lane).
+__device__ bool record_invalid_wave(const ChainEnv& E, uint64_t q, int32_t bs, bool strict) {
+  q = rfl_u64(q);
+  bs = (int32_t)rfl((uint32_t)bs);
+  return record_invalid_by(E, q, bs, strict, rec_fields(load_head(E.u, q)),
+                           [](const uint8_t* u, uint64_t c0, const RecFields& f, bool strict) {
+                             return cigar_facts_wave(u, c0, f, strict);
+                           });
 }
 
 __device__ __forceinline__ bool is_dead(const ChainEnv& E, uint64_t q) {
@@ -426,32 +435,12 @@ __device__ __forceinline__ bool dead_near(const ChainEnv& E, uint64_t q) {
 // first 36 + l_read_name bytes failed every candidate walk of its block, and
 // the block's search walked from every later candidate: ~7 ms on one 256 MiB
 // drop-in window.)
-__device__ __forceinline__ bool plausible(const ChainEnv& E, uint64_t q) {
-  if (q + 36 > E.e_inf) return E.e_inf < E.e_true && q + 4 <= E.e_inf && (int32_t)ldu32(E.u, q) >= 32;
-  const RecHead h = load_head(E.u, q);
-  int32_t bs = (int32_t)h.at(0);
-  int32_t ref = (int32_t)h.at(1);
-  int32_t pos = (int32_t)h.at(2);
-  uint32_t lrn = h.at(3) & 0xffu;
-  uint32_t ncig = h.at(4) & 0xffffu;
-  int32_t lseq = (int32_t)h.at(5);
-  int32_t nref = (int32_t)h.at(6);
-  int32_t npos = (int32_t)h.at(7);
-  if (ref < -1 || ref >= E.n_ref || nref < -1 || nref >= E.n_ref) return false;
-  if (pos < -1 || npos < -1 || lrn < 1 || lseq < 0) return false;
-  int64_t need = 32 + (int64_t)lrn + 4 * (int64_t)ncig + (int64_t)lseq + ((int64_t)lseq + 1) / 2;
-  if ((int64_t)bs < need) return false;
-  if (q + 4 + (uint64_t)bs > E.e_true) return false;
-  if (q + 36 + lrn > E.e_inf) return E.e_inf < E.e_true;
-  return E.u[q + 36 + lrn - 1] == 0;
-}
-
-// plausible() split for a software-pipelined walk: plausible_head decides
-// from q's head h alone (1: plausible, 0: not, 2: the read-name end byte at
+// The rules split for a software-pipelined walk: plausible_head decides from
+// q's head h alone (1: plausible, 0: not, 2: the read-name end byte at
 // q + 36 + lrn - 1 decides: *name_at = its position), so that a walk can
 // load that byte together with the next record's head (q + 4 + block_size):
-// one dependent memory round trip per record instead of two.  Same result
-// as plausible(E, q) when h = load_head(E.u, q).
+// one dependent memory round trip per record instead of two.  h =
+// load_head(E.u, q); it is not looked at when q + 4 > e_inf.
 __device__ __forceinline__ int plausible_head(const ChainEnv& E, uint64_t q, const RecHead& h, uint64_t* name_at) {
   if (q + 36 > E.e_inf) return E.e_inf < E.e_true && q + 4 <= E.e_inf && (int32_t)h.at(0) >= 32;
   int32_t bs = (int32_t)h.at(0);
@@ -471,6 +460,16 @@ __device__ __forceinline__ int plausible_head(const ChainEnv& E, uint64_t q, con
   *name_at = q + 36 + lrn - 1;
   return 2;
 }
+// the head of the record at q for plausible_head (a q whose block_size is
+// not inflated is not read: q0's bytes instead, which it does not look at)
+__device__ __forceinline__ RecHead plausible_load(const ChainEnv& E, uint64_t q, uint64_t q0) {
+  return load_head(E.u, q + 4 <= E.e_inf ? q : q0);
+}
+__device__ __forceinline__ bool plausible(const ChainEnv& E, uint64_t q) {
+  uint64_t name_at = 0;
+  const int ph = plausible_head(E, q, plausible_load(E, q, 0), &name_at);
+  return ph == 2 ? E.u[name_at] == 0 : ph != 0;
+}
 
 // plausible() at q and at the record after it (or the end / unreadable data):
 // a cheap second check that removes most false candidates inside long records.
@@ -484,10 +483,14 @@ __device__ __forceinline__ bool plausible2(const ChainEnv& E, uint64_t q) {
 // refID in range (random bytes pass with probability ~(n_ref / 2^32)^2), or
 // data past the inflated range, which plausible() judges itself.  Candidate
 // scans test it first and run plausible2 only when a lane of the wave passes.
+// (ref, nref: the dwords at q + 4 and q + 24, however the scan came by them;
+// branch-free, a scan evaluates it for 8 positions a lane)
+__device__ __forceinline__ bool refs_prefilter(const ChainEnv& E, int32_t ref, int32_t nref, uint64_t q) {
+  return (q + 36 > E.e_inf) | ((ref >= -1) & (ref < E.n_ref) & (nref >= -1) & (nref < E.n_ref));
+}
 __device__ __forceinline__ bool cand_prefilter(const ChainEnv& E, uint64_t q) {
-  if (q + 36 > E.e_inf) return true;
-  const int32_t ref = (int32_t)ldu32(E.u, q + 4), nref = (int32_t)ldu32(E.u, q + 24);
-  return ref >= -1 && ref < E.n_ref && nref >= -1 && nref < E.n_ref;
+  const bool inflated = q + 36 <= E.e_inf;  // (nothing is read past the inflated range)
+  return refs_prefilter(E, inflated ? (int32_t)ldu32(E.u, q + 4) : 0, inflated ? (int32_t)ldu32(E.u, q + 24) : 0, q);
 }
 
 // One chain step from q under the given rules.  Returns false if the walk
@@ -582,61 +585,6 @@ __global__ void k_rec_link_y(const uint64_t* __restrict__ g, const uint64_t* __r
   if (i < nb) y[i] = (g[i] != kNone && x[i] != kNone) ? x[i] : 0;
 }
 
-// Count (and validate) the records of each block of the span under the
-// reader / indexer rules.  One thread per block.
-//   cnt[i], err[i] = status code, errpos[i] = position of the failing record,
-//   *need = furthest byte the span needs inflated (atomicMax).
-template <int MODE>
-__global__ void k_rec_count(ChainEnv E, const uint64_t* __restrict__ entry, uint32_t* __restrict__ cnt,
-                            int32_t* __restrict__ err, unsigned long long* __restrict__ need) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t nb = E.k1 - E.k0;
-  if (i >= nb) return;
-  uint32_t n = 0;
-  int st = kOk;
-  const uint64_t e = entry[i];
-  if (e != kNone) {
-    const BlockInfo b = E.blocks[E.k0 + i];
-    const uint64_t lim = min(b.ustart + b.isize, E.q_end);
-    uint64_t q = e;
-    bool first = (MODE == kReader) && (e == E.p0);  // reader: first record follows a seek
-    while (q < lim) {
-      if (!first && is_dead(E, q)) {  // readInt at an exhausted block + empty block: EOF
-        st = kStopClean;
-        break;
-      }
-      first = false;
-      const uint64_t avail = E.e_true - q;
-      if (avail < 4) {
-        st = MODE == kIndexer && avail > 0 ? kErrIO : kStopClean;  // "less than 4 bytes long" / EOF
-        break;
-      }
-      if (q + 4 > E.e_inf) { atomicMax(need, (unsigned long long)(q + 4)); break; }
-      const int32_t bs = (int32_t)ldu32(E.u, q);
-      if (MODE == kReader) {
-        if (bs < 32) { st = kErrFormat; break; }
-        if (dead_in_record(E, q, bs) || avail - 4 < (uint64_t)bs) { st = kErrTrunc; break; }
-        if (q + 4 + (uint64_t)bs > E.e_inf) { atomicMax(need, (unsigned long long)(q + 4 + (uint64_t)bs)); break; }
-        const int32_t ref = (int32_t)ldu32(E.u, q + 4), nref = (int32_t)ldu32(E.u, q + 24);
-        if (ref < -1 || ref >= E.n_ref || nref < -1 || nref >= E.n_ref) { st = kErrArg; break; }
-        if (E.validate && record_invalid(E, q, bs, E.validate == 2)) { st = kErrFormat; break; }
-        ++n;
-        q += 4 + (uint64_t)bs;
-      } else {
-        ++n;
-        if (bs > 0) {
-          if ((uint64_t)bs > avail - 4 || is_dead(E, q + 4)) { st = kErrIO; break; }  // "Skip failed"
-          q += 4 + (uint64_t)bs;
-        } else {
-          q += 4;
-        }
-      }
-    }
-  }
-  cnt[i] = n;
-  err[i] = st;
-}
-
 // Second walk: write record positions and normalized voffs at base[i].
 template <int MODE>
 __global__ void k_rec_emit(ChainEnv E, const uint64_t* __restrict__ entry, const uint32_t* __restrict__ cnt,
@@ -659,30 +607,33 @@ __global__ void k_rec_emit(ChainEnv E, const uint64_t* __restrict__ entry, const
 }
 
 // ---------------------------------------------------------------------------
-// Record chain v2: lane-per-block walks with per-block record lists
+// The walk stage: a guessed chain and a list of record starts per block
 // ---------------------------------------------------------------------------
-//   k_rec_cand     one wave per block: first plausible record start (512
-//                  positions per step) -- where the block's guess walk begins.
-//   k_rec_walk     one lane per block: the chain from that candidate (next
-//                  candidates on failure), from the span start, or from a
-//                  forced (true) entry; every record start of the block is
-//                  listed as a u16 offset.  All walks of a span are in flight
-//                  at once, so the span costs one dependent-load chain of
-//                  ~records-per-block steps instead of a wave per block.
-//   k_rec_walk_wave  the unforced round of the two above in one launch, one
-//                  wave per block: a lane per 4 KiB segment walks from the
-//                  segment's first plausible start, and the lists are stitched
-//                  where the chain from the candidate meets them (the same g,
-//                  x, wcnt, lists and cand).  k_rec_cand + k_rec_walk remain
-//                  as its A/B (kStageWalkLane); k_rec_walk also runs the
-//                  forced re-walk rounds.
+//   k_rec_walk_wave  one wave per block: the block's first plausible record
+//                  start (its candidate), then a lane per 4 KiB segment walks
+//                  from the segment's first plausible start, and the lists are
+//                  stitched where the chain from the candidate meets them.
+//                  Every record start of the block is listed as a u16 offset
+//                  (g = the walk's start, x = its exit, wcnt = the count).
+//                  The block of the span start has a known entry: one lane
+//                  walks it by block_size alone (walk_entry).
+//   k_rec_cand + k_rec_walk  the same in two launches, a wave per block for the
+//                  candidate and a lane per block for the walk: the A/B of the
+//                  above (kStageWalkLane).  k_rec_walk also runs the forced
+//                  re-walk rounds of the link check.
+//   k_rec_search   blocks whose candidate's walk met an implausible record
+//                  (g == kRetry): the later candidates in order.
 //   k_rec_linkfix  max-scan link check; blocks whose list is off the chain are
 //                  re-walked from their true entry (usually zero or a few).
-//   k_rec_check_out  one wave per block: the reader / indexer rules of
-//                  k_rec_count for every listed record at once (the first stop
-//                  gives count, status and the bytes still to inflate), then
+//   k_rec_check_out  one wave per block: the reader / indexer rules
+//                  (check_listed_h) for every listed record at once (the first
+//                  stop gives count, status and the bytes still to inflate), then
 //                  positions, voffs and (reader) the fused decode + key at the
 //                  block's scanned base.
+// Shared by the walks: walk_plausible (every record must pass plausible(), to
+// a limit or to the block end and kGuessLookahead records beyond), walk_entry
+// (from a known entry by chain_step), wave_pull_block (the block into L2
+// before one lane's dependent loads).
 // k_rec_cand: one wave per block, each lane testing kCandPos consecutive
 // positions per step (512 per step): refID and mate refID of its 8 positions
 // come from 5 aligned 8 B loads, and only the rare position that passes that
@@ -721,8 +672,7 @@ __device__ __forceinline__ uint64_t cand_scan_wave(const ChainEnv& E, uint64_t l
         const uint64_t q = p0 + j;
         const int32_t ref = (int32_t)__builtin_amdgcn_alignbyte(w[2 + (j >> 2)], w[1 + (j >> 2)], j & 3);
         const int32_t nref = (int32_t)__builtin_amdgcn_alignbyte(w[7 + (j >> 2)], w[6 + (j >> 2)], j & 3);
-        const bool ok = (q >= lo) & (q < bend) &
-                        ((q + 36 > E.e_inf) | ((ref >= -1) & (ref < E.n_ref) & (nref >= -1) & (nref < E.n_ref)));
+        const bool ok = (q >= lo) & (q < bend) & refs_prefilter(E, ref, nref, q);
         pass |= ok ? 1u << j : 0u;
       }
       passes[t] = pass;
@@ -793,8 +743,7 @@ constexpr uint64_t kRetry = ~0ull - 2;  // g[]: the candidate's walk failed, sea
 constexpr uint32_t kListPlausible = 0x80000000u;  // wcnt flag: the list came from a plausible() walk
 constexpr uint32_t kListCountMask = 0x7fffffffu;
 
-// The plausible walk from `start`, shared by k_rec_walk's guess branch and
-// the pieces of k_rec_walk_wave: every record must pass plausible(); the
+// The plausible walk from `start`: every record must pass plausible(); the
 // records that start before lim are listed (put(index, position)).  With lim
 // == bend (the block end) the walk goes on for kGuessLookahead records past
 // the block end, or to the end of the stream or of the inflated range; with
@@ -817,7 +766,7 @@ __device__ __forceinline__ PlausWalk walk_plausible(const ChainEnv& E, uint64_t 
   bool valid = true;
   // (a start past the inflated range -- an exit handed on for its lookahead --
   // is not read: the loop ends before it looks at h)
-  RecHead h = load_head(E.u, start + 4 <= E.e_inf ? start : 0);
+  RecHead h = plausible_load(E, start, 0);
   int left = kGuessLookahead;  // plausible records required past the block end
   for (;;) {
     const bool inside = q < lim;
@@ -828,7 +777,7 @@ __device__ __forceinline__ PlausWalk walk_plausible(const ChainEnv& E, uint64_t 
     const uint8_t nb = E.u[na];
     // (q2 may lie anywhere: its head is loaded when its block_size is
     // inflated; reads reach 40 bytes past it, inside the stream's pad)
-    h = load_head(E.u, q2 + 4 <= E.e_inf ? q2 : q);
+    h = plausible_load(E, q2, q);
     if (ph == 0 || (ph == 2 && nb != 0)) { valid = false; break; }
     if (inside) {
       put(m, q);
@@ -840,6 +789,44 @@ __device__ __forceinline__ PlausWalk walk_plausible(const ChainEnv& E, uint64_t 
   return PlausWalk{valid, exitq, m};
 }
 
+// walk_plausible with nothing listed: is the chain from `start` plausible to
+// the block end and kGuessLookahead records beyond?
+__device__ __forceinline__ bool plausible_to_block_end(const ChainEnv& E, uint64_t start, uint64_t bend) {
+  return walk_plausible(E, start, bend, bend, [](uint32_t, uint64_t) {}).valid;
+}
+
+// The walk from a known entry (the span start, a forced entry, a candidate
+// whose chain was found plausible): by block_size alone (chain_step), every
+// record start before the block end listed in L.  Returns the count (it may
+// pass kListCap: the caller raises the overflow word), *exitq = where the
+// walk left the block or stopped.  One lane's work.
+template <int MODE>
+__device__ __forceinline__ uint32_t walk_entry(const ChainEnv& E, uint64_t entry, const BlockInfo& b,
+                                               uint16_t* __restrict__ L, uint64_t* exitq) {
+  const uint64_t bend = b.ustart + b.isize;
+  uint64_t q = entry, nq;
+  uint32_t n = 0;
+  while (q < bend) {
+    if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
+    ++n;
+    if (!chain_step<MODE>(E, q, &nq)) break;
+    q = nq;
+  }
+  *exitq = q;
+  return n;
+}
+
+// A lane's walk through a block is a chain of dependent loads from HBM (~190
+// for a short-read block).  The whole wave first pulls the block's inflated
+// bytes [lo, hi) and the lookahead past them into L2 with independent loads,
+// so that the chain then runs at L2 latency.
+__device__ __forceinline__ void wave_pull_block(const ChainEnv& E, uint64_t lo, uint64_t hi, uint32_t* overflow) {
+  uint32_t acc = 0;
+  const uint64_t end = min(hi + 4096, E.e_inf);
+  for (uint64_t a = (lo & ~127ull) + 128ull * lane_id(); a < end; a += 128ull * 64) acc += ldu32(E.u, a);
+  if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __restrict__ cand,
                                                   const uint64_t* __restrict__ force, uint64_t* __restrict__ g_out,
@@ -849,23 +836,14 @@ __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t nb = E.k1 - E.k0;
   if (force) {
-    // A re-walk round forces a few blocks; each is one lane's chain of ~190
-    // dependent loads from HBM.  The whole wave first pulls every forced
-    // block of the wave (+ the lookahead past its end) into L2 with
-    // independent loads, so the chain then runs at L2 latency.
+    // A re-walk round forces a few blocks, a lane each: the wave first pulls
+    // every forced block of the wave into L2.
     const uint64_t fi = i < nb ? force[i] : kNone;
-    uint64_t todo = __ballot(fi != kNone && fi != kForceEmpty);
-    uint32_t acc = 0;
-    const uint32_t lane = lane_id();
-    while (todo) {
+    for (uint64_t todo = __ballot(fi != kNone && fi != kForceEmpty); todo; todo &= todo - 1) {
       const uint32_t src = (uint32_t)__ffsll((long long)todo) - 1;
-      todo &= todo - 1;
       const BlockInfo wb = E.blocks[E.k0 + blockIdx.x * blockDim.x + (threadIdx.x & ~63u) + src];
-      const uint64_t lo = wb.ustart & ~127ull;
-      const uint64_t hi = min(wb.ustart + wb.isize + 4096, E.e_inf);
-      for (uint64_t a = lo + 128ull * lane; a < hi; a += 128ull * 64) acc += ldu32(E.u, a);
+      wave_pull_block(E, wb.ustart, wb.ustart + wb.isize, overflow);
     }
-    if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
   }
   if (i >= nb) return;
   uint64_t f = kNone;  // guess
@@ -879,15 +857,7 @@ __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __
     // a link-round entry may itself come from a wrong walk upstream (fixed in
     // the same round): re-walk only if the chain from it is plausible to the
     // block end and beyond; otherwise keep the old walk for the next round
-    uint64_t q = f;
-    bool ok = true;
-    int extra = 0;
-    while (ok) {
-      if (q >= bend && (extra++ >= kGuessLookahead || q == E.e_true || q + 36 > E.e_inf)) break;
-      if (!plausible(E, q)) ok = false;
-      else q += 4 + (uint64_t)(int32_t)ldu32(E.u, q);
-    }
-    if (!ok) return;
+    if (!plausible_to_block_end(E, f, bend)) return;
   }
   uint16_t* __restrict__ L = list + (uint64_t)i * kListCap;
   uint64_t g = kNone, x = kNone;
@@ -899,14 +869,7 @@ __global__ __launch_bounds__(256) void k_rec_walk(ChainEnv E, const uint64_t* __
     if (f == kNone && b.ustart <= E.p0) entry = E.p0;  // the block of the span start: entry known
     if (entry != kNone) {
       g = entry;
-      uint64_t q = entry, nq;
-      while (q < bend) {
-        if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
-        ++n;
-        if (!chain_step<MODE>(E, q, &nq)) break;
-        q = nq;
-      }
-      x = q;
+      n = walk_entry<MODE>(E, entry, b, L, &x);
     } else {
       const uint64_t c = cand[i];
       if (c < bend) {  // c == kNone (no candidate): nothing to walk
@@ -972,10 +935,6 @@ static_assert(kWalkSegs * kWalkSeg == kMaxIsize && kWalkSegs <= 64 && kWalkSegs 
 static_assert(kWalkProbe <= kWalkSeg, "a probe window inside its segment");
 constexpr uint32_t kPassRow = 64 + 4;  // a segment's 64 pass bytes (+ a word: rows on different banks)
 
-__device__ __forceinline__ uint64_t rfl_u64(uint64_t v) {
-  return (uint64_t)rfl((uint32_t)v) | ((uint64_t)rfl((uint32_t)(v >> 32)) << 32);
-}
-
 // (launch bounds: DESIGN.md 4.3, "k_rec_walk_wave")
 template <int MODE>
 __global__ __launch_bounds__(64, HBAM_WALK_WAVES) void k_rec_walk_wave(ChainEnv E, uint64_t* __restrict__ cand,
@@ -994,23 +953,13 @@ __global__ __launch_bounds__(64, HBAM_WALK_WAVES) void k_rec_walk_wave(ChainEnv 
   const bool live = bend > E.p0 && b.ustart < E.q_end && b.isize > 0;
   if (live && b.ustart <= E.p0) {
     // the block of the span start: the entry is known, the walk goes by
-    // block_size alone (chain_step).  One lane's chain of dependent loads:
-    // the wave pulls the block into L2 first with independent loads, as a
-    // forced re-walk does, so that the other blocks' waves do not wait on it.
-    uint32_t acc = 0;
-    const uint64_t hi = min(bend + 4096, E.e_inf);
-    for (uint64_t a = (b.ustart & ~127ull) + 128ull * lane; a < hi; a += 128ull * 64) acc += ldu32(E.u, a);
-    if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
+    // block_size alone (walk_entry).  One lane's chain of dependent loads:
+    // the wave pulls the block into L2 first, as a forced re-walk does, so
+    // that the other blocks' waves do not wait on it.
+    wave_pull_block(E, b.ustart, bend, overflow);
     if (lane == 0) {
       g = E.p0;
-      uint64_t q = E.p0, nq;
-      while (q < bend) {
-        if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
-        ++n;
-        if (!chain_step<MODE>(E, q, &nq)) break;
-        q = nq;
-      }
-      x = q;
+      n = walk_entry<MODE>(E, E.p0, b, L, &x);
     }
   } else if (live) {
     const uint32_t nseg = min((b.isize + kWalkSeg - 1) / kWalkSeg, kWalkSegs);
@@ -1040,7 +989,7 @@ __global__ __launch_bounds__(64, HBAM_WALK_WAVES) void k_rec_walk_wave(ChainEnv 
           const uint64_t q = p0 + k;
           const int32_t ref = (int32_t)__builtin_amdgcn_alignbyte(k < 4 ? r1 : r2, k < 4 ? r0 : r1, k & 3);
           const int32_t nref = (int32_t)__builtin_amdgcn_alignbyte(k < 4 ? m1 : m2, k < 4 ? m0 : m1, k & 3);
-          const bool ok = (q < bend) & ((q + 36 > E.e_inf) | ((ref >= -1) & (ref < E.n_ref) & (nref >= -1) & (nref < E.n_ref)));
+          const bool ok = (q < bend) & refs_prefilter(E, ref, nref, q);
           pass |= ok ? 1u << k : 0u;
         }
         s_pass[j0 + t][lane] = (uint8_t)(j0 + t < nseg ? pass : 0u);
@@ -1124,7 +1073,7 @@ __global__ __launch_bounds__(64, HBAM_WALK_WAVES) void k_rec_walk_wave(ChainEnv 
         n += pn;
         looked = klim == bend;  // that piece walked the lookahead
       }
-      if (ok && !looked) ok = rfl((uint32_t)walk_plausible(E, cur, bend, bend, [](uint32_t, uint64_t) {}).valid) != 0;
+      if (ok && !looked) ok = rfl((uint32_t)plausible_to_block_end(E, cur, bend)) != 0;
       if (ok) {
         g = c;
         x = cur;
@@ -1159,14 +1108,8 @@ __global__ __launch_bounds__(64) void k_rec_search(ChainEnv E, const uint64_t* _
   if (lane == 0) atomicAdd(searched, 1u);  // (hbam_chain_counters)
   const BlockInfo b = E.blocks[E.k0 + i];
   const uint64_t bend = b.ustart + b.isize;
-  {  // the walks below are dependent-load chains: pull the block (+ the
-     // lookahead past its end) into L2 first with independent loads
-    uint32_t acc = 0;
-    const uint64_t hi = min(bend + 4096, E.e_inf);
-    for (uint64_t a = (b.ustart & ~127ull) + 128ull * lane; a < hi; a += 128ull * 64) acc += ldu32(E.u, a);
-    if (acc == 0x9e3779b9u && E.k0 == 0xffffffffu) atomicOr(overflow, 0u);  // keeps the loads (never true)
-  }
-  uint64_t g = kNone, x = kNone;
+  wave_pull_block(E, b.ustart, bend, overflow);  // the walks below are dependent-load chains
+  uint64_t g = kNone;
   for (uint64_t c0 = cand[i] + 1; c0 < bend && g == kNone; c0 += 64) {
     const uint64_t p = c0 + lane;
     const bool pre = p < bend && cand_prefilter(E, p);
@@ -1174,35 +1117,19 @@ __global__ __launch_bounds__(64) void k_rec_search(ChainEnv E, const uint64_t* _
     while (m) {
       const uint64_t c = c0 + (uint64_t)(__ffsll((long long)m) - 1);
       m &= m - 1;
-      uint64_t q = c;
-      bool valid = true;
-      while (q < bend) {
-        if (!plausible(E, q)) { valid = false; break; }
-        q += 4 + (uint64_t)(int32_t)ldu32(E.u, q);
-      }
-      if (valid) {
-        uint64_t y = q;
-        for (int k = 0; k < kGuessLookahead; ++k) {
-          if (y == E.e_true || y + 36 > E.e_inf) break;
-          if (!plausible(E, y)) { valid = false; break; }
-          y += 4 + (uint64_t)(int32_t)ldu32(E.u, y);
-        }
-      }
-      if (valid) {
+      if (plausible_to_block_end(E, c, bend)) {
         g = c;
-        x = q;
         break;
       }
     }
   }
   if (lane == 0) {
+    // (every record of a plausible chain has a block_size that can be read
+    // and is >= 32: the walk by block_size leaves the block where it did)
     uint32_t n = 0;
+    uint64_t x = kNone;
     if (g != kNone) {
-      uint16_t* __restrict__ L = list + (uint64_t)i * kListCap;
-      for (uint64_t q = g; q < bend; q += 4 + (uint64_t)(int32_t)ldu32(E.u, q)) {
-        if (n < kListCap) L[n] = (uint16_t)(q - b.ustart);
-        ++n;
-      }
+      n = walk_entry<MODE>(E, g, b, list + (uint64_t)i * kListCap, &x);
       if (n > kListCap) atomicOr(overflow, 1u);
     }
     g_out[i] = g;
@@ -1263,10 +1190,16 @@ __global__ void k_force_from_entry(const uint64_t* __restrict__ g, const uint64_
   force[i] = e == gi ? kNone : (e == kNone ? kForceEmpty : e);
 }
 
-// The k_rec_count rules for the listed record at q (one lane): *stop = the
-// block's count ends at this record (*counted: the record itself counts),
-// *s = its status, *nd = bytes past the inflated range the record needs,
-// *long_cigar = its cigar was left to record_invalid_wave.
+// The reader / indexer rules for the record at q (one lane), stated here
+// once for the list path (k_rec_check_out) and the count path (k_rec_count):
+// *stop = the block's count ends at this record (*counted: the record itself
+// counts), *s = its status (kOk: a clean stop -- outside the span, EOF at a
+// dead position or at the end of the stream --, or with *nd set bytes still
+// to inflate), *nd = the furthest byte the record needs inflated, *long_cigar
+// = its cigar was left to a second pass (record_invalid_wave).
+// first: the reader's first record follows a seek (no EOF test at q);
+// light: the record passed plausible() on fully inflated data, which covers
+// every rule that reads it.
 template <int MODE>
 __device__ __forceinline__ void check_listed_h(const ChainEnv& E, uint64_t q, uint64_t lim, bool first, bool light,
                                                bool* stop, bool* counted, int* s, uint64_t* nd, bool* long_cigar,
@@ -1325,6 +1258,53 @@ __device__ __forceinline__ void check_listed_h(const ChainEnv& E, uint64_t q, ui
     }
   }
 }
+
+// The count path (a list overflowed: indexer-mode records shorter than 36
+// bytes): count and validate the records of each block by walking it, one
+// thread per block, check_listed_h per record.
+//   cnt[i], err[i] = status code (a stop that is no error: kStopClean),
+//   *need = furthest byte the span needs inflated (atomicMax).
+template <int MODE>
+__global__ void k_rec_count(ChainEnv E, const uint64_t* __restrict__ entry, uint32_t* __restrict__ cnt,
+                            int32_t* __restrict__ err, unsigned long long* __restrict__ need) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t nb = E.k1 - E.k0;
+  if (i >= nb) return;
+  uint32_t n = 0;
+  int st = kOk;
+  const uint64_t e = entry[i];
+  if (e != kNone) {
+    const BlockInfo b = E.blocks[E.k0 + i];
+    const uint64_t lim = min(b.ustart + b.isize, E.q_end);
+    uint64_t q = e;
+    bool first = (MODE == kReader) && (e == E.p0);  // reader: first record follows a seek
+    while (q < lim) {  // (the walk leaves the block: no head is loaded past its end)
+      bool stop = false, counted = false, long_cigar = false;
+      int s = kOk;
+      uint64_t nd = 0;
+      const RecHead h = load_head(E.u, q);
+      check_listed_h<MODE>(E, q, lim, first, false, &stop, &counted, &s, &nd, &long_cigar, h);
+      first = false;
+      const int32_t bs = (int32_t)h.at(0);
+      // a cigar above kWaveCigarOps operators: one lane's pass takes any length
+      if (long_cigar && record_invalid_h(E, q, bs, E.validate == 2, nullptr, h)) {
+        stop = true;
+        s = kErrFormat;
+      }
+      if (stop) {
+        n += counted;
+        if (nd) atomicMax(need, (unsigned long long)nd);
+        else st = s == kOk ? kStopClean : s;
+        break;
+      }
+      ++n;
+      q += 4 + (uint64_t)(MODE == kReader ? bs : (bs > 0 ? bs : 0));
+    }
+  }
+  cnt[i] = n;
+  err[i] = st;
+}
+
 // Record check and output in one pass (the list path of decode_span_pos):
 // the record rules, the long-cigar validation and the output, one wave per
 // block, so a block's records are read from HBM once after inflate and
@@ -1363,8 +1343,8 @@ __global__ __launch_bounds__(64, 6) void k_rec_check_out(ChainEnv E, const uint6
   const uint64_t lim = min(b.ustart + b.isize, E.q_end);
   const uint32_t wc = wcnt[i];
   const uint32_t listed = e == kNone ? 0u : min(wc & kListCountMask, kListCap);
-  // (check_block's rules) a plausible() list on fully inflated data already
-  // satisfies every rule that reads the record
+  // (check_listed_h's light) a plausible() list on fully inflated data
+  // already satisfies every rule that reads the record
   const bool light = (wc & kListPlausible) && E.e_inf == E.e_true && (MODE != kReader || E.validate == 0);
   const uint64_t o0 = base[i];
   uint32_t count = listed;
@@ -1398,7 +1378,7 @@ __global__ __launch_bounds__(64, 6) void k_rec_check_out(ChainEnv E, const uint6
     }
     if (MODE == kReader) {
       // cigars longer than kWaveCigarOps before the stop, a wave each in order
-      // (k_rec_check_long): the first invalid one becomes the stop
+      // (record_invalid_wave): the first invalid one becomes the stop
       const bool lg = lane < m && long_cigar;
       for (uint64_t wm = __ballot(lg); wm; wm &= wm - 1) {
         const uint32_t src = (uint32_t)__ffsll((long long)wm) - 1;

@@ -7,7 +7,7 @@ import struct
 import bai
 import orc
 from hbam import synth
-from test_gpu_windows import recompress
+from bam_patch import recompress
 
 
 def spread_bam(n_records, placement, seed=0x48424D00, block_payload=65280):

@@ -16,7 +16,7 @@ import numpy as np
 
 import orc
 import sort_cases as sc
-from test_gpu_windows import recompress
+from bam_patch import recompress
 
 ORDER = "queryname"
 FLAGS = (0x0, 0x1, 0x41, 0x81, 0xC1, 0x141, 0x841, 0x4)  # tie words 6, 2, 0, 4, 2, 1, 1, 6

@@ -19,7 +19,7 @@ import orc
 from bai_cases import spread_bam
 from hbam import synth
 from test_bai import PLACEMENTS
-from test_gpu_windows import recompress
+from bam_patch import recompress
 
 INT32_MAX = (1 << 31) - 1
 ALL = (1 << 64) - 1

@@ -15,7 +15,7 @@ import bai
 import orc
 from conftest import GOLDEN
 from hbam import synth
-from test_gpu_windows import recompress
+from bam_patch import recompress
 
 ORDERS = ("key", "coordinate")
 TILE = 32768  # output bytes per workgroup of the gather

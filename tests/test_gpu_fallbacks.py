@@ -29,15 +29,22 @@ pytestmark = pytest.mark.gpu
 ALL = (1 << 64) - 1
 
 
-def _with_eof_stop():
-    """3,000 records, an EOF block, then 3,000 more from a block start."""
+def _with_eof_stop(break_record=None):
+    """3,000 records, an EOF block, then 3,000 more from a block start
+    (break_record: that one of them with a wrong bin, a STRICT-only error)."""
     d1, _ = synth.make_bam(3000, eof_block=True)
     d2, _ = synth.make_bam(3000, seed=99, eof_block=False)
     s2 = orc.Stream(d2)
     # file 2's records re-cut into blocks that start at its first record, so
     # that the chain goes on through them past file 1's EOF block: the reader
     # stops at the empty block (no error), and the walks list records after it
-    recs = bytes(s2.data)[s2.header_end:]
+    recs = bytearray(s2.data[s2.header_end:])
+    if break_record is not None:
+        q = 0
+        for _ in range(break_record):
+            q += 4 + struct.unpack_from("<i", recs, q)[0]
+        struct.pack_into("<H", recs, q + 14, 1)
+    recs = bytes(recs)
     lens = [min(65280, len(recs) - a) for a in range(0, len(recs), 65280)]
     return d1 + orc.bgzf_compress(recs, lens, level=5, eof=True)
 
@@ -56,6 +63,37 @@ def test_records_after_an_eof_block_take_the_separate_launches():
         st = f.decode_span_device(f.header()["first_record_voff"], ALL)
         assert st["records"] == 3000 and st["status"] == 0
         assert f.splitting_index(5) == s.splitting_index(5)
+
+
+def test_an_invalid_record_after_an_eof_block():
+    """(a) with a STRICT-invalid record among the records listed after the
+    EOF block.  From the file's start the reader stops at the empty block
+    before it reaches that record: 3,000 records, status 0 -- the verdict on
+    a record listed past the first stop never becomes the span's.  A span
+    that starts at the block after the EOF block reaches it: the records up
+    to it and the oracle's status.  (Reader-mode lists cannot overflow --
+    kListCap holds every start of records of 36 bytes or more -- so both go
+    through k_rec_check_out; k_rec_count runs for the indexer only, below.)"""
+    d1, _ = synth.make_bam(3000, eof_block=True)
+    data = _with_eof_stop(break_record=700)
+    assert data[:len(d1)] == d1
+    s = orc.Stream(data)
+    rc, want = s.decode_all()
+    assert rc == 0 and len(want["key"]) == 3000
+    rc2, want2 = s.decode_span(len(d1) << 16, ALL)
+    assert rc2 == 1 and len(want2["key"]) == 700
+    with hbam.BamFile(data, window_bytes=1 << 30) as f:
+        c0 = f.pipeline_counters()
+        got = f.decode_all()
+        assert got["status"] == 0
+        assert_same_records(got, want)
+        assert f.pipeline_counters()["records_after_stop"] > c0["records_after_stop"]
+        got2 = f.decode_span(len(d1) << 16, ALL, raise_on_error=False)
+        assert got2["status"] == rc2
+        # (the span's first position is the end of the empty block as well as
+        # the start of the next: the oracle names it by the former)
+        np.testing.assert_array_equal(got2["key"], want2["key"])
+        np.testing.assert_array_equal(got2["voff"][1:], want2["voff"][1:])
 
 
 @pytest.mark.parametrize("eof_mid", [False, True])

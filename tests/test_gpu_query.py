@@ -12,7 +12,7 @@ import bai
 import hbam
 import orc
 import query_cases as q
-from test_gpu_windows import recompress
+from bam_patch import recompress
 
 pytestmark = pytest.mark.gpu
 WINDOWS = [0, 65536]

@@ -7,32 +7,17 @@ Small windows force many windows on small files, so every path that a 60 GB
 file takes runs here in seconds."""
 import os
 import struct
-import zlib
 
 import numpy as np
 import pytest
 
 import hbam
 import orc
+from bam_patch import patched as _patched
 from hbam import synth
 from test_gpu_parity import FIELDS, assert_same_records
 
 ALL = (1 << 64) - 1
-
-
-def recompress(stream, u: bytes) -> bytes:
-    """The stream's blocks re-cut from new inflated bytes u (zlib level 5):
-    a valid BGZF file carrying whatever records u holds."""
-    out = bytearray()
-    for b in stream.blocks:
-        a, n = int(b["ustart"]), int(b["isize"])
-        raw = bytes(u[a:a + n])
-        co = zlib.compressobj(5, zlib.DEFLATED, -15)
-        c = co.compress(raw) + co.flush()
-        total = 18 + len(c) + 8
-        out += bytes([0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF, 6, 0, 66, 67, 2, 0]) + struct.pack("<H", total - 1)
-        out += c + struct.pack("<II", zlib.crc32(raw) & 0xFFFFFFFF, n)
-    return bytes(out)
 
 
 def _digest(r):
@@ -142,14 +127,6 @@ def test_prefetch_then_device_decode():
         st = f.decode_span_device(f.header()["first_record_voff"], ALL, timing=True)
         assert f.bytes_read() == n0  # every window attached to the HBM copy
         assert st["records"] == len(want["key"]) and (st["key_xor"], st["voff_sum"]) == _digest(want)
-
-
-def _patched(data, rec, offset, fmt, value):
-    s = orc.Stream(data, stringency=orc.SILENT)
-    rc, r = s.decode_all()
-    u = bytearray(s.data)
-    struct.pack_into(fmt, u, int(r["offset"][rec]) + offset, value)
-    return recompress(s, bytes(u))
 
 
 # (record, byte offset in the record, struct format, value): each breaks one

@@ -7,7 +7,8 @@ and test.bam -- which the reference reads under htsjdk's default STRICT in
 TestSplittingBAMIndexer.java:27-32 -- passes every rule.  Parity with htsjdk
 itself is unpinned beyond that (no JVM here; no reference test asserts a
 validation error).  The GPU rules are compared with the oracle in
-test_gpu_windows.py."""
+test_gpu_strict.py (record by record, both cigar passes) and
+test_gpu_windows.py (whole files)."""
 import struct
 
 import numpy as np
@@ -120,7 +121,7 @@ def test_stringency_levels_in_oracle_decode():
     u = bytearray(s.data)
     p = int(r["offset"][1700])
     struct.pack_into("<H", u, p + 14, 1)  # wrong bin: a STRICT-only error
-    from test_gpu_windows import recompress
+    from bam_patch import recompress
     bad = recompress(s, bytes(u))
     for st, want_rc, want_n in ((orc.STRICT, 1, 1700), (orc.LENIENT, 0, 3000), (orc.SILENT, 0, 3000)):
         rc, got = orc.Stream(bad, stringency=st).decode_all()
